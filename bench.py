@@ -14,6 +14,12 @@ own B chains (the vintage/chain parfor shards with no data-path collective),
 so scaling is weak; the only collectives are the timing barrier and the
 max-reduction of the elapsed time.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times
+the N steps and prints the result line.  `--dump-outputs DIR` also writes the last
+timed step's stored draw as DIR/<name>.npy.  Everything else (CPU baselines, the
+predictive-density, block-hybrid, hybrid, S120, GIRF and OOS lines) runs only
+with `--full`.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -46,6 +52,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--chains", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and the secondary lines (predictive density, block hybrid, "
+                         "hybrid, S120, GIRF, OOS); the options below select among them (--s120-only stands alone: a "
+                         "probe of the S120 line that needs no --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the draw the last timed step stored (PAI, PHI, invA, sqrtht of every chain) as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of the chains beyond 64 MB in all, the "
+                         "limit shared equally by the ranks of --gpus N)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="budget per process of each CPU-oracle baseline line (rank 0, N=1 only)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -78,13 +92,56 @@ def parse():
                          "the full bench run (112, 4) fell to 89.4 while (112, 2) holds 104.3, profiles/r04z_*)")
     ap.add_argument("--s120-groups", type=int, default=2,
                     help="chain groups (HIP streams driven from host threads) of the S120 lines")
-    ap.add_argument("--s120-only", action="store_true", help="run only the S120 lines (probe)")
+    ap.add_argument("--s120-only", action="store_true", help="run only the S120 lines and print one line each (probe; instead of the main line, "
+                         "with or without --full)")
     ap.add_argument("--girf-draws", type=int, default=256,
                     help="MCMC draws of the block-hybrid GIRF line (generateGIRF2blockhybrid, 1000 shock "
                          "paths x 120 horizons x 12 sims per draw); 0 = skip")
     ap.add_argument("--cpu-workers", type=int, default=0,
                     help="parallel single-thread CPU baseline processes (0: min(16, cpus))")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+STORE_CAP = 32             # draws the main line's device store holds (41.8 MB each at 256 chains)
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def sweep_stored(ch, n, cap):
+    """n stored sweeps of a chain set whose draw store holds `cap` draws: one ccmm_chains_sweep call
+    while they fit (the default run), else a call per store-full with the store emptied in between
+    (get_draws without a destination resets it and copies nothing, but it synchronises the stream:
+    beyond `cap` sweeps the timed region holds one such drain per `cap` sweeps, negligible beside
+    `cap` sweeps of ~10 ms each)."""
+    while n > 0:
+        if ch.stored() >= cap:
+            ch.get_draws(which=())
+        k = min(n, cap - ch.stored())
+        ch.sweep(k, store=True)
+        n -= k
+
+
+def dump_outputs(dirname, draws, rank, world=1):
+    """--dump-outputs: the last stored draw of every array of get_draws() (what the last timed step
+    handed the caller), chain axis last, as <name>.npy (rank > 0: <name>.rank<r>.npy) in float64.
+    Beyond DUMP_MAX_BYTES in all (each of `world` ranks takes an equal share), a fixed seeded sample of
+    the chains is written (chains.npy lists it)."""
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    last = {k.replace("_all", ""): np.asarray(v[-1], dtype=np.float64) for k, v in draws.items()}
+    B = next(iter(last.values())).shape[-1]
+    total = sum(a.nbytes for a in last.values())
+    keep = np.arange(B)
+    limit = DUMP_MAX_BYTES // world
+    if total + 8 * B > limit:
+        nb = max(1, int(B * (limit - 8 * B) // total))
+        keep = np.sort(np.random.default_rng(20220901).choice(B, nb, replace=False))
+    sfx = f".rank{rank}" if rank else ""
+    np.save(out / f"chains{sfx}.npy", keep.astype(np.float64))
+    for name, a in last.items():
+        np.save(out / f"{name}{sfx}.npy", np.ascontiguousarray(a[..., keep]))
 
 
 def launch_ranks(n):
@@ -134,7 +191,7 @@ def main():
         return
 
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         # before the GPU is initialised: the baseline runs in spawned single-thread processes
         _progress("cpu baseline")
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_workers)
@@ -153,7 +210,7 @@ def main():
         name, val = kv.split("=")
         ctx.set_option(name, int(val))
         pkg.samplers.context(local).set_option(name, int(val))
-    cap = args.warmup + args.steps
+    cap = min(args.warmup + args.steps, STORE_CAP)
     ch = pkg.Chains(ctx, N=m.N, p=p, T=m.T, B=B, crn=False, store_capacity=cap,
                     seed=1012023 + 7919 * rank)
     ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
@@ -168,12 +225,12 @@ def main():
             dist.barrier()
 
     _progress("main line")
-    ch.sweep(args.warmup, store=True)
+    sweep_stored(ch, args.warmup, cap)
     barrier()
     if not args.no_profile:
         ch.profile(True)
     t0 = time.perf_counter()
-    ch.sweep(args.steps, store=True)
+    sweep_stored(ch, args.steps, cap)
     barrier()
     elapsed = time.perf_counter() - t0
     ktimes = ch.kernel_times() if not args.no_profile else {}
@@ -182,31 +239,33 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    draws = ch.get_draws()
+    # the draws still in the store (at most `cap`): all four arrays for the dump, else PAI alone (a quarter
+    # of the bytes) for the finiteness check
+    draws = ch.get_draws() if args.dump_outputs else ch.get_draws(which=("PAI_all",))
     assert np.all(np.isfinite(draws["PAI_all"])), "non-finite draws"
     ch.close()
-    fc = bench_predictive(pkg, ctx, d, B) if (rank == 0 and not args.no_fcst) else None
-    # secondary lines (configs[2], configs[3]) run on every rank: own barrier/max-reduction
-    bh = None
-    _progress("secondary lines")
-    if args.bh_steps > 0:
-        bh = [bench_block_hybrid(pkg, ctx, d, int(b), args, rank, barrier, dist)
-              for b in args.bh_chains.split(",") if b.strip()]
-    hy = None
-    if args.hy_steps > 0:
-        hy = [bench_hybrid(pkg, ctx, d, int(b), args, rank, barrier, dist)
-              for b in args.hy_chains.split(",") if b.strip()]
-    s120 = None
-    if args.s120_steps > 0:
-        s120 = [bench_s120(pkg, ctx, int(b), args, rank, barrier, dist)
-                for b in args.s120_chains.split(",") if b.strip()]
-    girf = None
-    if args.girf_draws > 0:
-        girf = bench_girf(pkg, ctx, d, args.girf_draws, rank, barrier, dist)
-    oos = None
-    if args.oos_steps > 0:
-        oos = [bench_oos(pkg, ctx, d, int(c), args, rank, barrier, dist, floor=(i == 0))
-               for i, c in enumerate(x for x in args.oos_chains.split(",") if x.strip())]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, draws, rank, world)
+    del draws
+    fc = bh = hy = s120 = girf = oos = None
+    if args.full:
+        fc = bench_predictive(pkg, ctx, d, B) if (rank == 0 and not args.no_fcst) else None
+        # secondary lines (configs[2], configs[3]) run on every rank: own barrier/max-reduction
+        _progress("secondary lines")
+        if args.bh_steps > 0:
+            bh = [bench_block_hybrid(pkg, ctx, d, int(b), args, rank, barrier, dist)
+                  for b in args.bh_chains.split(",") if b.strip()]
+        if args.hy_steps > 0:
+            hy = [bench_hybrid(pkg, ctx, d, int(b), args, rank, barrier, dist)
+                  for b in args.hy_chains.split(",") if b.strip()]
+        if args.s120_steps > 0:
+            s120 = [bench_s120(pkg, ctx, int(b), args, rank, barrier, dist)
+                    for b in args.s120_chains.split(",") if b.strip()]
+        if args.girf_draws > 0:
+            girf = bench_girf(pkg, ctx, d, args.girf_draws, rank, barrier, dist)
+        if args.oos_steps > 0:
+            oos = [bench_oos(pkg, ctx, d, int(c), args, rank, barrier, dist, floor=(i == 0))
+                   for i, c in enumerate(x for x in args.oos_chains.split(",") if x.strip())]
 
     if rank != 0:
         if dist is not None:
