@@ -28,6 +28,10 @@ MODEL_HYBRID = 2  # mcmcVARhybridGibbs.m: K = N*p + 1 + Ns*p
 MODEL_SHADOWRATE = 3  # mcmcVARshadowrate.m: shadow-rate design for all equations, linear forecasts
 
 RNG_PAI, RNG_A, RNG_SVU, RNG_SVZ, RNG_PHI, RNG_ELB, RNG_FCST, RNG_PS = 1, 2, 3, 4, 5, 6, 7, 8
+RNG_PSALT = 9  # randn(nmiss,1) of the alternate draw (mcmcVARshadowrateBlockHybrid.m:471-475)
+STATUS_PS = 128  # missing-data / alternate draw: precision not positive definite (invalid draws)
+# treatment of the ELB months (ccmm_chains_set_elb_treatment); _PAIR: MISSING by the unfused kernel pair
+ELB_TREAT_SHADOW, ELB_TREAT_MISSING, ELB_TREAT_MISSING_PAIR = 0, 1, 2
 CCMM_WARN_MVNCDF = 3
 
 _dp = C.POINTER(C.c_double)
@@ -138,6 +142,8 @@ _SIGS = {
     "ccmm_chains_get_cta_gram": (C.c_int, [C.c_void_p, _dp]),
     "ccmm_chains_get_cta_factor": (C.c_int, [C.c_void_p, _dp]),
     "ccmm_chains_set_elb_ps": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ccmm_chains_set_elb_treatment": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ccmm_ps_draw1_resident": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "ccmm_draw_summaries": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp,
                                       _dp, _dp, _dp]),
     "ccmm_girf_hybrid": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
@@ -198,6 +204,15 @@ def load_library(path: str | os.PathLike | None = None):
 
 def exported_symbols():
     return list(_SIGS)
+
+
+def ps_draw1_resident(W: int, elbTmax: int, nmax: int) -> bool:
+    """Whether the one-draw kernel (k_ps_draw1, band width W in 16/32/48/64) keeps the band factor of nmax
+    censored cells in LDS (ccmm_ps_draw1_resident; host-only, no device needed)."""
+    rc = load_library().ccmm_ps_draw1_resident(int(W), int(elbTmax), int(nmax))
+    if rc < 0:
+        raise ValueError(f"ccmm_ps_draw1_resident: {last_error()}")
+    return bool(rc)
 
 
 def last_error() -> str:
@@ -727,6 +742,8 @@ class Chains:
             blocks.append(("FCST", 2 * N * self.fH * self.fNd, "n"))
         if getattr(self, "ps_np", 0):
             blocks.append(("PS", self.Ns * self.elbTmax * self.ps_np, "n"))
+        if getattr(self, "elb_alternate", False):
+            blocks.append(("PSALT", self.Ns * self.elbTmax, "n"))
         out, o = {}, 0
         for name, n, kind in blocks:
             out[name] = (o, n, kind)
@@ -938,7 +955,25 @@ class Chains:
         m >= ps_from_m (1-based; the reference: ceil(MCMCburnin / 2)); 0 proposals disables."""
         _check(self.lib.ccmm_chains_set_elb_ps(self.handle, int(nproposals), int(ps_from_m)),
                "ccmm_chains_set_elb_ps")
-        self.ps_np = int(nproposals)
+        if not getattr(self, "elb_missing", False):
+            self.ps_np = int(nproposals)
+
+    def set_elb_treatment(self, missing=False, alternate=False, *, fused=True):
+        """Treatment of the ELB months (ccmm_chains_set_elb_treatment; after set_elb_model, before set_state).
+        missing: doELBsampling = false (mcmcVARshadowrateBlockHybrid.m:481-499) -- every sweep takes one
+        unconstrained draw of the censored cells as the data, kept as missingrate, shadowrate_all NaN.
+        alternate: doELBsampleAlternate with doELBsampling = true (block hybrid, :470-475) -- one more such
+        draw per sweep, kept as missingrate only.  fused=False is unsupported (tools/probe_missingdata.py only,
+        CCMM_ELB_TREAT_MISSING_PAIR): the missing-data draw by the unfused kernel pair, same bits."""
+        t = ELB_TREAT_SHADOW if not missing else (ELB_TREAT_MISSING if fused else ELB_TREAT_MISSING_PAIR)
+        _check(self.lib.ccmm_chains_set_elb_treatment(self.handle, t, int(bool(alternate))),
+               "ccmm_chains_set_elb_treatment")
+        was = getattr(self, "elb_missing", False)
+        self.elb_missing, self.elb_alternate = bool(missing), bool(alternate)
+        if missing:
+            self.ps_np = 1  # the CRN record of set_elb_ps(1, .)
+        elif was:
+            self.ps_np = 0
 
     def get_ps(self):
         """countAccept, countAcceptBurnin (B) and stackAccept (M x B, 0 = none) of the

@@ -288,6 +288,11 @@ struct ccmm_chains {
   // m = ps_from_m on (1-based, m = sweep + 1; the reference: m >= MCMCburnin/2, :435)
   int ps_np = 0, ps_from_m = -1, psW = 0, ps_nmax = 0;
   bool ps_dirty = true;
+  // treatment of the ELB months (ccmm_chains_set_elb_treatment): elb_missing = every sweep takes one
+  // unconstrained draw as the data (held as ps_np = 1 from sweep 1: the CRN record and the condition
+  // records of set_elb_ps(1, .)); elb_alt = one more such draw per sweep, kept as missingrate only
+  bool elb_missing = false, elb_alt = false;
+  bool ps_rec() const { return ps_np > 0 || elb_alt; }  // the condition records carry the PS part
   DBuf<double> eEtPS, psL, psY;
   DBuf<int> psCell, psN, psAcc, psFlag, psCount, sAccept;
   int stored = 0;
@@ -574,6 +579,10 @@ struct ccmm_chains {
       crn_off[CCMM_RNG_PS] = o;
       o += (int64_t)cf.Ns * cf.elbTmax * ps_np;
     }
+    if (bh && elb_alt) {  // randn(nmiss, 1) of the alternate draw (:471-475), last
+      crn_off[CCMM_RNG_PSALT] = o;
+      o += (int64_t)cf.Ns * cf.elbTmax;
+    }
     crn_len = o;
   }
 
@@ -721,7 +730,7 @@ struct ccmm_chains {
     eY0.alloc(B * ET * N);
     eYt.alloc(B * ET * N);
     eEt.alloc(B * ET * N);
-    eCond.alloc(B * ET * (size_t)elb_cond_stride(cfg.Ns, cfg.p, ps_np > 0));
+    eCond.alloc(B * ET * (size_t)elb_cond_stride(cfg.Ns, cfg.p, ps_rec()));
     eScur.alloc(B * ET * Ns);
     HIPCHECK(hipMemset(eScur.p, 0, eScur.n * sizeof(double)));
   }
@@ -753,7 +762,7 @@ struct ccmm_chains {
     e.Et = eEt.p;
     e.cond = eCond.p;
     e.Scur = eScur.p;
-    e.condStride = elb_cond_stride(cfg.Ns, cfg.p, ps_np > 0);
+    e.condStride = elb_cond_stride(cfg.Ns, cfg.p, ps_rec());
     e.kshadow = cfg.N * cfg.p + 1;
     e.K = cfg.K;
     e.mode = elb_mode;
@@ -1364,15 +1373,20 @@ struct ccmm_chains {
       sShadow.alloc(B * cap * cfg.Ns * cfg.elbTmax);
       ElbDev e = elb_view();
       launch(KID_STORE, [&] {
-        hipLaunchKernelGGL(k_elb_store, dim3(d.B), dim3(256), 0, ctx->stream, e, cs, sShadow.p,
-                           cfg.store_capacity, stored);
+        if (elb_missing)  // shadowrate = NaN (:492; mcmcVARshadowrate.m:448)
+          hipLaunchKernelGGL(k_ps_first_store, dim3(d.B), dim3(256), 0, ctx->stream, (const double*)nullptr, e.elbT,
+                             cs.slot, sShadow.p, cfg.Ns * cfg.elbTmax, cfg.Ns, cfg.store_capacity, stored);
+        else
+          hipLaunchKernelGGL(k_elb_store, dim3(d.B), dim3(256), 0, ctx->stream, e, cs, sShadow.p,
+                             cfg.store_capacity, stored);
       });
       if (keep_first) {  // missingrate_all (mcmcVARshadowrate.m:498)
         sMissing.alloc(B * cap * cfg.Ns * cfg.elbTmax);
         ElbDev e2 = elb_view();
         launch(KID_STORE, [&] {
           hipLaunchKernelGGL(k_ps_first_store, dim3(d.B), dim3(256), 0, ctx->stream,
-                             (last_ps && psFirst.p) ? psFirst.p : nullptr, e2.elbT, cs.slot, sMissing.p,
+                             ((last_ps || elb_missing || elb_alt) && psFirst.p) ? psFirst.p : nullptr, e2.elbT,
+                             cs.slot, sMissing.p,
                              cfg.Ns * cfg.elbTmax, cfg.Ns, cfg.store_capacity, stored);
         });
       }
@@ -1380,7 +1394,7 @@ struct ccmm_chains {
         sAccept.alloc(B * cap);
         launch(KID_STORE, [&] {
           hipLaunchKernelGGL(k_ps_store, dim3((d.B + 255) / 256), dim3(256), 0, ctx->stream,
-                             last_ps ? psFlag.p : nullptr, sAccept.p, d.B, cfg.store_capacity, stored);
+                             (last_ps && !elb_missing) ? psFlag.p : nullptr, sAccept.p, d.B, cfg.store_capacity, stored);
         });
       }
     }
@@ -1390,15 +1404,31 @@ struct ccmm_chains {
   // ---------------------------------------------------------------- PS branch
   void set_elb_ps(int np, int from_m) {
     require(np >= 0 && np <= (1 << 20), "Nproposals must be in [0, 2^20]");
-    const int old = ps_np;
     ps_np = np;
     ps_from_m = np > 0 ? from_m : -1;
-    if ((old > 0) != (np > 0) && cfg.elbTmax > 0) {
+    if (cfg.elbTmax > 0) {  // (no-op unless the records grow: the PS part)
       const size_t B = cfg.B, ET = std::max(cfg.elbTmax, 1);
-      eCond.alloc(B * ET * (size_t)elb_cond_stride(cfg.Ns, cfg.p, np > 0));
+      eCond.alloc(B * ET * (size_t)elb_cond_stride(cfg.Ns, cfg.p, ps_rec()));
     }
     ps_dirty = true;
     layout_crn();
+  }
+  void set_elb_treatment(bool missing, bool alternate, bool pair) {
+    require(!(missing && alternate), "CCMM_ELB_TREAT_MISSING: alternate must be 0 (the draw is the treatment)");
+    require(!alternate || cfg.model == CCMM_MODEL_BLOCKHYBRID,
+            "the alternate draw is the block hybrid's (mcmcVARhybridGibbs.m:488-496 has it commented out)");
+    require(!missing || elb_missing || ps_np == 0,
+            "CCMM_ELB_TREAT_MISSING takes no PS proposals: call ccmm_chains_set_elb_ps(ch, 0, 0) first");
+    require(stored == 0, "ccmm_chains_set_elb_treatment: call before storing draws");
+    const bool was = elb_missing;
+    elb_missing = missing;
+    elb_alt = alternate;
+    draw1_pair = pair;
+    if (missing || alternate) keep_first = true;  // the draw is missingrate_all
+    if (missing)
+      set_elb_ps(1, 1);
+    else
+      set_elb_ps(was ? 0 : ps_np, was ? 0 : ps_from_m);
   }
   // band width of the censored-cell precision and the largest cell count over the slots
   void ps_layout() {
@@ -1456,21 +1486,76 @@ struct ccmm_chains {
     ps.flag = psFlag.p;
     ps.count = psCount.p;
     ps.per = cfg.Ns * std::max(cfg.elbTmax, 1);
-    ps.first = keep_first ? psFirst.p : nullptr;
+    ps.first = (keep_first && !elb_missing && !elb_alt) ? psFirst.p : nullptr;  // (else: the draw's buffer)
     ps.state = psState.p;
     ps.epoch = ps_epoch;
+    ps.draw1 = 0;
+    ps.out = nullptr;
     return ps;
   }
   // missingrate_all (mcmcVARshadowrate.m:435, 498; mcmcVARhybridGibbs.m:486): keep proposal 1 of
   // every PS sweep in the draw store (ccmm_chains_keep_missingrate)
   bool keep_first = false;
+  bool draw1_pair = false;  // CCMM_ELB_TREAT_MISSING_PAIR: the draw by k_ps_chol_w + k_ps_apply (timing)
   DBuf<double> psFirst, sMissing;
   int last_ps = 0;  // whether the last ELB step ran the PS branch (draw store bookkeeping)
 
   void run_ps(const RngArgs& ra, ElbDev& e, bool kept) {
-    ChainState cs = view();
     if (keep_first) psFirst.alloc((size_t)d.B * cfg.Ns * std::max(cfg.elbTmax, 1));
     const PsDev ps = ps_view();
+    run_ps_chol(e, ps);
+    if (ps.first) {  // proposal 1's uncensored cells are the window's data (the chain's current Y)
+      HIPCHECK(hipMemcpyAsync(psFirst.p, e.Scur, (size_t)d.B * ps.per * sizeof(double), hipMemcpyDeviceToDevice,
+                              ctx->stream));
+    }
+    run_ps_apply(e, ps, ra, kept, true);
+    e.psFlag = psFlag.p;
+  }
+
+  // One unconstrained draw of the censored cells per chain from the sweep's condition records (draw1 = 1:
+  // the missing-data treatment, into the chain's shadow rates; 2: the alternate draw), kept in psFirst as
+  // the sweep's missingrate.  fused: k_ps_draw1 (W <= 64), else k_ps_chol(_w) then k_ps_apply taking
+  // proposal 1 unconditionally (the only form above 64; the timing probe runs both)
+  void run_draw1(const RngArgs& ra, const ElbDev& e, int draw1, bool fused) {
+    ChainState cs = view();
+    psFirst.alloc((size_t)d.B * cfg.Ns * std::max(cfg.elbTmax, 1));
+    PsDev ps = ps_view();
+    ps.draw1 = draw1;
+    ps.out = draw1 == 1 ? e.Scur : psFirst.p;
+    const size_t bytes = (size_t)d.B * ps.per * sizeof(double);
+    if (draw1 == 2)  // the observed cells of missingrate are the window's data
+      HIPCHECK(hipMemcpyAsync(psFirst.p, e.Scur, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (fused && psW <= 64) {
+      const int ET = std::max(cfg.elbTmax, 1);
+      const int res = ps_draw1_resident(psW, ET, ps_nmax);
+      const size_t lds = ps_draw1_lds_bytes(psW, ET, ps_nmax, res);
+      require(lds <= kPsLdsBudget, "PS branch: cell list does not fit LDS");
+      launch(KID_PSCHOL, [&] {
+        switch (psW) {
+#define CASE_PSD(W)                                                                                              \
+  case W:                                                                                                        \
+    HIPCHECK(hipFuncSetAttribute((const void*)k_ps_draw1<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_ps_draw1<W>, dim3(d.B), dim3(64), lds, ctx->stream, d, e, ps, cs, ra, res);             \
+    break;
+          CASE_PSD(16)
+          CASE_PSD(32)
+          CASE_PSD(48)
+          CASE_PSD(64)
+#undef CASE_PSD
+          default:
+            throw ArgError("PS band width");
+        }
+      });
+    } else {
+      run_ps_chol(e, ps);
+      run_ps_apply(e, ps, ra, false, false);
+    }
+    if (draw1 == 1)
+      HIPCHECK(hipMemcpyAsync(psFirst.p, e.Scur, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+
+  void run_ps_chol(const ElbDev& e, const PsDev& ps) {
+    ChainState cs = view();
     // option ps_chol_lds: the first-generation k_ps_chol (LDS window) for every band width (same factor)
     if (psW <= 64 && !opt[OPT_PS_CHOL_LDS]) {  // register-window factorisation, one wave per chain (k_ps_chol_w)
       const size_t lds = ps_chol_w_lds_bytes(psW, std::max(cfg.elbTmax, 1), ps_nmax);
@@ -1499,18 +1584,21 @@ struct ccmm_chains {
         hipLaunchKernelGGL(k_ps_chol, dim3(d.B), dim3(128), lds, ctx->stream, d, e, ps, cs);
       });
     }
-    if (ps.first) {  // proposal 1's uncensored cells are the window's data (the chain's current Y)
-      HIPCHECK(hipMemcpyAsync(psFirst.p, e.Scur, (size_t)d.B * ps.per * sizeof(double), hipMemcpyDeviceToDevice,
-                              ctx->stream));
-    }
+  }
+
+  void run_ps_apply(const ElbDev& e, const PsDev& ps, const RngArgs& ra, bool kept, bool prop) {
     launch(KID_PSPROP, [&] {
       const dim3 g((ps_np + 255) / 256, d.B);
       switch (psW) {
 #define CASE_PSW(W)                                                                                   \
   case W:                                                                                             \
-    hipLaunchKernelGGL(k_ps_prop<W>, g, dim3(256), 0, ctx->stream, e, ps, ra);                        \
-    hipLaunchKernelGGL(k_ps_apply<W>, dim3(d.B), dim3(64), (size_t)ps_nmax * sizeof(double), ctx->stream, e, \
-                       ps, ra, kept ? 1 : 0);                                                           \
+    if (prop) hipLaunchKernelGGL(k_ps_prop<W>, g, dim3(256), 0, ctx->stream, e, ps, ra);              \
+    if (ps.draw1)                                                                                     \
+      hipLaunchKernelGGL((k_ps_apply<W, true>), dim3(d.B), dim3(64), (size_t)ps_nmax * sizeof(double),  \
+                         ctx->stream, e, ps, ra, 0);                                                    \
+    else                                                                                              \
+      hipLaunchKernelGGL((k_ps_apply<W, false>), dim3(d.B), dim3(64), (size_t)ps_nmax * sizeof(double), \
+                         ctx->stream, e, ps, ra, kept ? 1 : 0);                                         \
     break;
         CASE_PSW(16)
         CASE_PSW(32)
@@ -1522,16 +1610,15 @@ struct ccmm_chains {
           throw ArgError("PS band width");
       }
     });
-    e.psFlag = psFlag.p;
   }
 
   void run_elb(const RngArgs& ra, bool kept) {
     if (cfg.elbTmax <= 0) return;
     ChainState cs = view();
     ElbDev e = elb_view();
-    const bool ps = ps_active();
+    const bool ps = ps_active() && !elb_missing;
     last_ps = ps ? 1 : 0;
-    if (ps) {
+    if (ps || elb_missing || elb_alt) {
       ps_layout();
       e = elb_view();
       e.ps = 1;
@@ -1610,6 +1697,8 @@ struct ccmm_chains {
     // speculative Gibbs step (option elb_spec, small B): the asynchronous wave kernels start beside the PS
     // branch on a stream of their own and stop once it accepts; the draw is kept only for a rejected PS
     // (the reference's order and draws: PS first, the Gibbs draw the fallback, :438-466)
+    // (option ps_chol_lds selects k_ps_chol, which only the unfused pair can run)
+    if (elb_missing) run_draw1(ra, e, 1, !draw1_pair && !opt[OPT_PS_CHOL_LDS]);
     const bool spec = ps && opt[OPT_ELB_SPEC] && d.B <= kElbMpMaxB && !use_oct && W > 1 && opt[OPT_ELB_ASYNC] &&
                       elb_flags == nullptr;
     hipStream_t gst = ctx->stream;
@@ -1634,7 +1723,9 @@ struct ccmm_chains {
     } else if (ps) {
       run_ps(ra, e, kept);
     }
-    if (use_oct) {
+    if (elb_missing) {
+      // no Gibbs kernel: the draw is the data (:498)
+    } else if (use_oct) {
       launch(KID_ELBGIBBS, [&] {
         switch (Ns) {
 #define CASE_NSO(NS)                                                                                           \
@@ -1742,6 +1833,9 @@ struct ccmm_chains {
       hipLaunchKernelGGL(k_elb_spec_select, dim3(d.B), dim3(256), 0, ctx->stream, ep, slot.p, d.B);
       HIPCHECK(hipGetLastError());
     }
+    // the alternate draw (:470-475): this sweep's precision and linear term (the condition records above,
+    // which hold the observed data only), into the missingrate buffer alone
+    if (elb_alt) run_draw1(ra, e, 2, !opt[OPT_PS_CHOL_LDS]);
     const int nrb = e.elbTmax * Ns * (p + 1);
     launch(KID_ELBREBUILD, [&] {
       hipLaunchKernelGGL(k_elb_rebuild, dim3((nrb + 255) / 256, d.B), dim3(256), 0, ctx->stream, d, e,
@@ -3413,10 +3507,37 @@ int ccmm_chains_set_elb_ps(ccmm_chains* ch, int nproposals, int ps_from_m) {
     require(ch != nullptr, "null argument");
     require(ch->bh, "chain set was not created with CCMM_MODEL_BLOCKHYBRID / CCMM_MODEL_HYBRID");
     require(nproposals == 0 || ps_from_m >= 1, "ps_from_m must be >= 1");
+    require(!ch->elb_missing || nproposals == 0,
+            "CCMM_ELB_TREAT_MISSING takes no PS proposals (ccmm_chains_set_elb_treatment)");
+    if (ch->elb_missing) return 0;  // (the treatment's own single draw stays configured)
     HIPCHECK(hipSetDevice(ch->ctx->device));
     HIPCHECK(hipStreamSynchronize(ch->ctx->stream));
     ch->set_elb_ps(nproposals, ps_from_m);
     return 0;
+  });
+}
+
+int ccmm_chains_set_elb_treatment(ccmm_chains* ch, int treatment, int alternate) {
+  return guarded([&] {
+    require(ch != nullptr, "null argument");
+    require(ch->bh, "chain set has no ELB step (block-hybrid, hybrid and shadow-rate models only)");
+    require(treatment == CCMM_ELB_TREAT_SHADOW || treatment == CCMM_ELB_TREAT_MISSING ||
+                treatment == CCMM_ELB_TREAT_MISSING_PAIR,
+            "unknown ELB treatment");
+    require(alternate == 0 || alternate == 1, "alternate must be 0 or 1");
+    HIPCHECK(hipSetDevice(ch->ctx->device));
+    HIPCHECK(hipStreamSynchronize(ch->ctx->stream));
+    ch->set_elb_treatment(treatment != CCMM_ELB_TREAT_SHADOW, alternate != 0,
+                          treatment == CCMM_ELB_TREAT_MISSING_PAIR);
+    return 0;
+  });
+}
+
+int ccmm_ps_draw1_resident(int W, int elbTmax, int nmax) {
+  return guarded([&] {
+    require(W == 16 || W == 32 || W == 48 || W == 64, "W must be 16, 32, 48 or 64");
+    require(elbTmax >= 0 && nmax >= 0, "negative size");
+    return ps_draw1_resident(W, elbTmax, nmax);
   });
 }
 

@@ -98,12 +98,28 @@ struct PsDev {
   int per;          // Ns elbTmax
   unsigned long long* state;  // [B] speculative Gibbs step: epoch << 1 | accepted, posted by k_ps_apply
   unsigned long long epoch;   //     (nullptr / 0: no Gibbs step waits on the decision)
+  // one unconstrained draw per sweep (ccmm_chains_set_elb_treatment): 0 the accept-first branch, 1 the
+  // missing-data treatment (the draw becomes the data), 2 the alternate draw (block CCMM_RNG_PSALT)
+  int draw1;
+  double* out;      // [B][Ns elbTmax] where the draw goes: the chain's shadow rates / the missingrate buffer
 };
 
 constexpr int kPsChunk = 64;  // assembled band rows per LDS chunk
 
 __host__ __device__ inline size_t ps_chol_w_lds_bytes(int W, int elbTmax, int nmax) {
   return (size_t)(kPsChunk * W + kPsChunk + W) * sizeof(double) + (size_t)(elbTmax + nmax) * sizeof(int);
+}
+
+// k_ps_draw1: k_ps_chol_w's LDS, L^-1 b and the draw's normals (nmax doubles each), the cells' shadow-rate
+// offsets (nmax ints) and, when resident, the nmax x W band rows of L
+__host__ __device__ inline size_t ps_draw1_lds_bytes(int W, int elbTmax, int nmax, int resident) {
+  return ps_chol_w_lds_bytes(W, elbTmax, nmax) + (size_t)2 * nmax * sizeof(double) + (size_t)nmax * sizeof(int) +
+         (resident ? (size_t)nmax * W * sizeof(double) : 0);
+}
+constexpr size_t kPsLdsBudget = 160 * 1024;
+// whether k_ps_draw1 keeps the factor's band rows in LDS (else it reads them back from PsDev::L)
+inline int ps_draw1_resident(int W, int elbTmax, int nmax) {
+  return ps_draw1_lds_bytes(W, elbTmax, nmax, 1) <= kPsLdsBudget ? 1 : 0;
 }
 
 // ---------------------------------------------------------------- kernels (ccmm_elb.hip)
@@ -121,8 +137,9 @@ __global__ void k_elb_store(ElbDev e, ChainState cs, double* out, int cap, int m
 // ---------------------------------------------------------------- kernels (ccmm_ps.hip)
 __global__ void k_ps_chol(Dims d, ElbDev e, PsDev ps, ChainState cs);
 template <int W> __global__ void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, ChainState cs);
+template <int W> __global__ void k_ps_draw1(Dims d, ElbDev e, PsDev ps, ChainState cs, RngArgs ra, int resident);
 template <int W> __global__ void k_ps_prop(ElbDev e, PsDev ps, RngArgs ra);
-template <int W> __global__ void k_ps_apply(ElbDev e, PsDev ps, RngArgs ra, int kept);
+template <int W, bool FORCED> __global__ void k_ps_apply(ElbDev e, PsDev ps, RngArgs ra, int kept);
 __global__ void k_ps_first_store(const double* first, const int* elbT, const int* slot, double* out, int per,
                                  int Ns, int cap, int m);
 __global__ void k_ps_store(const int* flag, int* out, int B, int cap, int m);

@@ -18,7 +18,7 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // ---------------------------------------------------------------- RNG
 // Philox4x32-10 (Salmon et al. 2011), counter = (pair index, chain, sweep, block),
 // key = 64-bit seed.  Two doubles per call; normals by Box-Muller.
-constexpr int kRngBlocks = 9;  // CCMM_RNG_* ids 1..8
+constexpr int kRngBlocks = 10;  // CCMM_RNG_* ids 1..9
 
 struct u32x4 {
   uint32_t x, y, z, w;

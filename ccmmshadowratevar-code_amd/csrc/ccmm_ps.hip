@@ -20,10 +20,22 @@
 //              by an LDS then a global atomic min
 //   k_ps_apply per chain: recompute the accepted proposal into the chain's shadow rates
 //              (k_elb_gibbs skips those chains), bookkeeping of :453-460
+//
+// The missing-data treatment (doELBsampling = false, :481-499) and the alternate draw (:470-475) take one
+// such draw per sweep unconditionally: k_ps_draw1, one wave per chain, factors, solves and substitutes
+// in one launch (below).
 #include "ccmm_elb.h"
 
 namespace ccmm {
 
+// not positive definite: no proposals, the Gibbs draw serves the sweep (bit 64, informational; k_phi sets
+// bit 16 concurrently).  The missing-data treatment and the alternate draw have no Gibbs draw behind them:
+// bit 128, invalid.  n = 0 makes whatever substitutes next (k_ps_prop / k_ps_apply, forced or not) leave the
+// chain alone, as k_ps_draw1 does by returning: the cells, or the missingrate buffer, stay as they were
+__device__ inline void ps_fail(const PsDev& ps, const ChainState& cs, int c) {
+  ps.n[c] = 0;
+  atomicOr(&cs.status[c], ps.draw1 ? CCMM_STATUS_PS : CCMM_STATUS_PS_GIBBS);
+}
 
 // ---------------------------------------------------------------- banded Cholesky
 // One thread per band row (64 threads, 128 for band widths above 64: Ns = 5 with p = 12)
@@ -110,12 +122,7 @@ __global__ __launch_bounds__(128) void k_ps_chol(Dims d, ElbDev e, PsDev ps, Cha
     }
     __syncthreads();
   }
-  if (fail) {  // not positive definite: no proposals, the Gibbs draw serves the sweep
-    if (lane == 0) {
-      ps.n[c] = 0;
-      atomicOr(&cs.status[c], CCMM_STATUS_PS_GIBBS);  // informational (k_phi sets bit 16 concurrently)
-    }
-  }
+  if (fail && lane == 0) ps_fail(ps, cs, c);  // not positive definite
 }
 
 // ---------------------------------------------------------------- banded Cholesky, register window
@@ -130,16 +137,20 @@ __global__ __launch_bounds__(128) void k_ps_chol(Dims d, ElbDev e, PsDev ps, Cha
 // the window in LDS (and its serial assembly of the cell list).  Same band storage, same updates
 // (fma(-L(i,k), L(j,k), A(i,j)) and bb -= L(i,k) yk) in the same order per entry.
 
-template <int W>
-__global__ __launch_bounds__(64) void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, ChainState cs) {
+// The factorisation of one chain by one wave: fills ps.cell / ps.n / ps.L / ps.ybar of chain c and returns
+// the cell count n (0: no censored cell), fail = a pivot was not positive.  prow: the kernel's LDS doubles
+// (kPsChunk W + kPsChunk + W), scens: its LDS ints (elbTmax + nmax).  KEEP (k_ps_draw1): ybar also goes to
+// ybl[n] and, when Ll is set, the band rows to Ll[n][W], both in LDS, for the substitution that follows
+// in the same kernel.
+template <int W, bool KEEP>
+__device__ __forceinline__ int ps_chol_w_core(const ElbDev& e, const PsDev& ps, const ChainState& cs, int c,
+                                              double* prow, int* scens, double* Ll, double* ybl, bool& fail) {
   static_assert(W >= 2 && W <= 64, "one wave: W <= 64");
-  extern __shared__ double sm[];
-  double* prow = sm;                  // kPsChunk x W: P(i, i - W + 1 + cc) of row i at [(i - base) W + cc]
+  // prow: kPsChunk x W: P(i, i - W + 1 + cc) of row i at [(i - base) W + cc]
   double* pb = prow + kPsChunk * W;   // kPsChunk: b(i) of the chunk's rows
   double* sL = pb + kPsChunk;         // W: pivot column L(k + r, k) at [r]
-  int* scens = (int*)(sL + W);        // elbTmax: month of censored month ci
+  // scens: elbTmax: month of censored month ci
   int* info = scens + e.elbTmax;      // nmax: (censored-month index << 3) | variable
-  const int c = blockIdx.x;
   const int s = cs.slot[c];
   const int lane = threadIdx.x;
   const int Ns = e.Ns, p = e.p;
@@ -170,7 +181,7 @@ __global__ __launch_bounds__(64) void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, Ch
   __syncthreads();
   for (int i = lane; i < n; i += 64) ps.cell[(size_t)c * ps.nmax + i] = scens[info[i] >> 3] * Ns + (info[i] & 7);
   if (lane == 0) ps.n[c] = n;
-  if (n == 0) return;
+  if (n == 0) return 0;
   const double* recs = e.cond + (size_t)c * e.elbTmax * e.condStride;
   const int xo = elb_cond_ps_off(Ns, p);
   auto pentry = [&](int i, int j) -> double {  // P(i, j), i >= j (as k_ps_chol)
@@ -202,7 +213,7 @@ __global__ __launch_bounds__(64) void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, Ch
   int r = lane < W ? lane : W;  // the lane's row relative to the pivot row (W: idle lane)
   double* Lg = ps.L + (size_t)c * ps.nmax * W;
   double* yb = ps.ybar + (size_t)c * ps.nmax;
-  bool fail = false;
+  fail = false;
   int sk = 0;  // the pivot row's lane, k mod W
   for (int k = 0; k < n; ++k) {
     const double dkk = readlane_d(reg[0], sk);
@@ -213,8 +224,12 @@ __global__ __launch_bounds__(64) void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, Ch
     if (r < W) {
       Lg[(size_t)k * W + r] = l;
       sL[r] = l;
+      if (KEEP && Ll) Ll[(size_t)k * W + r] = l;
     }
-    if (lane == sk) yb[k] = yk;
+    if (lane == sk) {
+      yb[k] = yk;
+      if (KEEP) ybl[k] = yk;
+    }
     wave_lds_sync();
 #pragma unroll
     for (int cc = 1; cc < W; ++cc) reg[cc] = fma(-l, sL[cc], reg[cc]);
@@ -243,10 +258,17 @@ __global__ __launch_bounds__(64) void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, Ch
     r = (r == 0) ? W - 1 : (r < W ? r - 1 : W);
     sk = (sk + 1 == W) ? 0 : sk + 1;
   }
-  if (fail && lane == 0) {  // not positive definite: no proposals, the Gibbs draw serves the sweep
-    ps.n[c] = 0;
-    atomicOr(&cs.status[c], CCMM_STATUS_PS_GIBBS);  // informational (k_phi sets bit 16 concurrently)
-  }
+  return n;
+}
+
+template <int W>
+__global__ __launch_bounds__(64) void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, ChainState cs) {
+  extern __shared__ double sm[];
+  const int c = blockIdx.x;
+  bool fail = false;
+  const int n = ps_chol_w_core<W, false>(e, ps, cs, c, sm, (int*)(sm + kPsChunk * W + kPsChunk + W), nullptr,
+                                         nullptr, fail);
+  if (n && fail && threadIdx.x == 0) ps_fail(ps, cs, c);
 }
 
 // x = L'^-1 (ybar + z_k): one proposal by back substitution, the W - 1 values x_{i+1..i+W-1}
@@ -342,14 +364,15 @@ __device__ inline bool ps_backsub(const double* __restrict__ Lc, const double* _
 
 // The normals of cell i and of cell i - 1 of proposal k, as ps_backsub takes them (i odd: the two
 // halves of one Box-Muller pair under Philox), for a parallel fill: lanes take cells in pairs.
-__device__ inline void ps_normal_pair(const Rng& rng, int n, int k, int i, double& zi, double& zim1) {
+__device__ inline void ps_normal_pair(const Rng& rng, int n, int k, int i, double& zi, double& zim1,
+                                      int block = CCMM_RNG_PS) {
   if (rng.crn) {
-    zi = rng.normal(CCMM_RNG_PS, (uint32_t)(i + n * k));
-    zim1 = (i >= 1) ? rng.normal(CCMM_RNG_PS, (uint32_t)(i - 1 + n * k)) : 0.0;
+    zi = rng.normal(block, (uint32_t)(i + n * k));
+    zim1 = (i >= 1) ? rng.normal(block, (uint32_t)(i - 1 + n * k)) : 0.0;
     return;
   }
   const uint32_t idx = (uint32_t)((n + (n & 1)) * k) + (uint32_t)i;
-  const u32x4 r = rng.raw(CCMM_RNG_PS, idx >> 1);
+  const u32x4 r = rng.raw(block, idx >> 1);
   const double u1 = u01(r.x, r.y), u2 = u01(r.z, r.w);
   const double rad = sqrt(-2.0 * log(u1));
   double sn, cs;
@@ -385,18 +408,41 @@ __global__ __launch_bounds__(256) void k_ps_prop(ElbDev e, PsDev ps, RngArgs ra)
   if (threadIdx.x == 0 && kmin != INT_MAX) atomicMin(ps.acc + c, kmin);
 }
 
+// The n normals of proposal k into zl, by all lanes of one wave: cells in pairs from the top,
+// (n - 1, n - 2), ... (n odd under Philox: the top cell alone first)
+__device__ inline void ps_fill_normals(const Rng& rng, int n, int k, int lane, double* zl, int block) {
+  const bool lone = !rng.crn && (n & 1);
+  if (lone && lane == 0) {
+    double zi, zj;
+    ps_normal_pair(rng, n, k, n - 1, zi, zj, block);
+    zl[n - 1] = zi;
+  }
+  const int top = lone ? n - 2 : n - 1;  // cell top is a pair's upper half
+  for (int q = lane; 2 * q <= top; q += 64) {
+    const int i = top - 2 * q;
+    double zi, zj;
+    ps_normal_pair(rng, n, k, i, zi, zj, block);
+    zl[i] = zi;
+    if (i >= 1) zl[i - 1] = zj;
+  }
+}
+
 // One wave per chain: the accepted proposal's normals are formed by all lanes (Box-Muller pairs in
 // parallel) into LDS, then lane 0 substitutes it into the chain's shadow rates (the serial chain
-// then waits on the substitution only, not on a log / sqrt / sincos per two cells)
-template <int W>
+// then waits on the substitution only, not on a log / sqrt / sincos per two cells).
+// FORCED (ps.draw1: missing-data treatment / alternate draw at band widths above 64, and the unfused pair
+// of timing comparisons): proposal 1 is taken whatever its cells, written to ps.out, and no acceptance
+// is booked
+template <int W, bool FORCED>
 __global__ __launch_bounds__(64) void k_ps_apply(ElbDev e, PsDev ps, RngArgs ra, int kept) {
   extern __shared__ double zl[];  // [nmax]
   const int c = blockIdx.x;
   const int lane = threadIdx.x;
   const int n = ps.n[c];
-  const int kmin = ps.acc[c];
+  constexpr bool forced = FORCED;
+  const int kmin = forced ? 0 : ps.acc[c];
   if (n == 0 || kmin == INT_MAX) {
-    if (lane == 0) {
+    if (lane == 0 && !forced) {
       ps.acc[c] = INT_MAX;
       if (n == 0 && ps.first)  // no proposals this sweep (precision not positive definite)
         for (int q = 0; q < ps.per; ++q) ps.first[(size_t)c * ps.per + q] = __builtin_nan("");
@@ -406,30 +452,58 @@ __global__ __launch_bounds__(64) void k_ps_apply(ElbDev e, PsDev ps, RngArgs ra,
     return;
   }
   const Rng rng = ra.make(c);
-  // cells in pairs from the top: (n - 1, n - 2), ... (n odd under Philox: the top cell alone first)
-  const bool lone = !rng.crn && (n & 1);
-  if (lone && lane == 0) {
-    double zi, zj;
-    ps_normal_pair(rng, n, kmin, n - 1, zi, zj);
-    zl[n - 1] = zi;
-  }
-  const int top = lone ? n - 2 : n - 1;  // cell top is a pair's upper half
-  for (int q = lane; 2 * q <= top; q += 64) {
-    const int i = top - 2 * q;
-    double zi, zj;
-    ps_normal_pair(rng, n, kmin, i, zi, zj);
-    zl[i] = zi;
-    if (i >= 1) zl[i - 1] = zj;
-  }
+  ps_fill_normals(rng, n, kmin, lane, zl, (forced && ps.draw1 == 2) ? CCMM_RNG_PSALT : CCMM_RNG_PS);
   __syncthreads();
   if (lane == 0) {
-    ps.acc[c] = INT_MAX;
+    double* out = forced ? ps.out + (size_t)c * ps.per : e.Scur + (size_t)c * e.elbTmax * e.Ns;
+    if (!forced) ps.acc[c] = INT_MAX;
     (void)ps_backsub<W>(ps.L + (size_t)c * ps.nmax * W, ps.ybar + (size_t)c * ps.nmax, n, rng, kmin, ps.elb,
-                        e.Scur + (size_t)c * e.elbTmax * e.Ns, ps.cell + (size_t)c * ps.nmax, zl);
+                        out, ps.cell + (size_t)c * ps.nmax, zl);
+    if (forced) return;
     ps.flag[c] = kmin + 1;
     ps.count[2 * c + (kept ? 1 : 0)] += 1;
     if (ps.state) __hip_atomic_store(&ps.state[c], ps.epoch << 1 | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// ---------------------------------------------------------------- one draw per chain, one launch
+// The missing-data treatment of the ELB months (doELBsampling = false,
+// mcmcVARshadowrateBlockHybrid.m:481-499; mcmcVARhybridGibbs.m:499-518; mcmcVARshadowrate.m:442-459) and
+// the alternate draw (:470-475) take exactly one unconstrained draw of the censored cells per sweep.
+// One wave per chain does k_ps_chol_w's factorisation (ps_chol_w_core: the same code), forms the draw's
+// normals with all lanes and substitutes with lane 0 (ps_backsub, as k_ps_apply): bit-identical to
+// proposal 1 of the PS branch.  The band rows of L stay in LDS for the substitution when they fit
+// (ps_draw1_resident: the reference window, W = 48 and 276 cells, 106 KB); otherwise the substitution
+// reads them back from ps.L, which the factorisation writes in either case (ccmm_chains_get_ps_mean).
+// The draw goes to ps.out (the chain's shadow rates, or the missingrate buffer of the alternate draw)
+// whether or not it lies below the ELB.  No waiting between workgroups; the only atomic is the status bit.
+template <int W>
+__global__ __launch_bounds__(64) void k_ps_draw1(Dims d, ElbDev e, PsDev ps, ChainState cs, RngArgs ra,
+                                                 int resident) {
+  extern __shared__ double sm[];
+  double* ybl = sm + kPsChunk * W + kPsChunk + W;  // nmax: L^-1 b
+  double* zl = ybl + ps.nmax;                       // nmax: the draw's normals
+  double* Ll = zl + ps.nmax;                        // nmax x W band rows (resident)
+  int* scens = (int*)(Ll + (resident ? (size_t)ps.nmax * W : 0));
+  int* cellL = scens + e.elbTmax + ps.nmax;         // nmax: shadow-rate offset of cell i
+  const int c = blockIdx.x;
+  const int lane = threadIdx.x;
+  bool fail = false;
+  const int n = ps_chol_w_core<W, true>(e, ps, cs, c, sm, scens, resident ? Ll : nullptr, ybl, fail);
+  if (n == 0) return;
+  if (fail) {  // not positive definite: the cells stay as they were
+    if (lane == 0) ps_fail(ps, cs, c);
+    return;
+  }
+  const int* info = scens + e.elbTmax;
+  for (int i = lane; i < n; i += 64) cellL[i] = scens[info[i] >> 3] * e.Ns + (info[i] & 7);
+  const Rng rng = ra.make(c);
+  ps_fill_normals(rng, n, 0, lane, zl, ps.draw1 == 2 ? CCMM_RNG_PSALT : CCMM_RNG_PS);
+  if (!resident) __threadfence();  // the band rows written to ps.L above are read back below
+  __syncthreads();
+  if (lane == 0)
+    (void)ps_backsub<W>(resident ? Ll : ps.L + (size_t)c * ps.nmax * W, ybl, n, rng, 0, ps.elb,
+                        ps.out + (size_t)c * ps.per, cellL, zl);
 }
 
 // missingrate_all(thisMCMCdraw,:,:) = missingrate (mcmcVARshadowrate.m:498): proposal 1 of a PS
@@ -456,7 +530,14 @@ template __global__ void k_ps_chol_w<48>(Dims, ElbDev, PsDev, ChainState);
 template __global__ void k_ps_chol_w<64>(Dims, ElbDev, PsDev, ChainState);
 #define CCMM_PS_INST(W)                                                 \
   template __global__ void k_ps_prop<W>(ElbDev, PsDev, RngArgs);        \
-  template __global__ void k_ps_apply<W>(ElbDev, PsDev, RngArgs, int);
+  template __global__ void k_ps_apply<W, false>(ElbDev, PsDev, RngArgs, int);  \
+  template __global__ void k_ps_apply<W, true>(ElbDev, PsDev, RngArgs, int);
+#define CCMM_PS_DRAW1(W) template __global__ void k_ps_draw1<W>(Dims, ElbDev, PsDev, ChainState, RngArgs, int);
+CCMM_PS_DRAW1(16)
+CCMM_PS_DRAW1(32)
+CCMM_PS_DRAW1(48)
+CCMM_PS_DRAW1(64)
+#undef CCMM_PS_DRAW1
 CCMM_PS_INST(16)
 CCMM_PS_INST(32)
 CCMM_PS_INST(48)

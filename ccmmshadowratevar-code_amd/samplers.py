@@ -100,6 +100,13 @@ def _run_with_predictive_density(ch, m, burn, MCMCdraws, ndxYIELDS, ELBbound, yr
             fc["yhatsum"] / MCMCdraws] + scores
 
 
+def _refuse_gibbs_on_nan(where):
+    raise NotImplementedError(
+        "doELBsampling=false with doELBsampleAlternate=false: the reference then calls "
+        f"gibbsdrawShadowrates on data holding NaN ({where}), so no defined behaviour exists; "
+        "pass doELBsampleAlternate=true for the missing-data treatment")
+
+
 def _run_chain_set(ch, burn, MCMCdraws, doprogress, step=50):
     done = 0
     while done < burn:
@@ -126,8 +133,12 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
                                  burnin=None, gibbsburn=100, Nproposals=1000, elb_ps=True,
                                  stats=None):
     """mcmcVARshadowrateBlockHybrid.m:1-14, outputs PAI_all, PHI_all, invA_all,
-    sqrtht_all, shadowrate_all (M x Nshadowrates x elbT), missingrate_all (NaN: the draw of the
-    doELBsampleAlternate branch, off in every reference driver, :470-478).
+    sqrtht_all, shadowrate_all (M x Nshadowrates x elbT), missingrate_all (NaN unless
+    doELBsampleAlternate: then the sweep's extra unconstrained draw, :470-478).
+
+    doELBsampling=False with doELBsampleAlternate=True is the missing-data treatment (:481-499,
+    doVARshadowrateBlockHybridMissingData.m): every sweep one unconstrained draw of the censored cells
+    becomes the data, missingrate_all holds it and shadowrate_all is NaN (:492).
 
     The ELB step follows :433-466: the Gibbs sampler for m < MCMCburnin/2, then the
     acceptance-sampling branch (Nproposals draws of the precision sampler restated from
@@ -138,12 +149,12 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     if check_stationarity:
         raise NotImplementedError("check_stationarity=1 is not supported; the reference drivers "
                                   "all pass 0")
-    if not doELBsampling or doELBsampleAlternate:
-        raise NotImplementedError("doELBsampling=false / doELBsampleAlternate=true need the "
-                                  "missing-data sampler VARTVPSVprecisionsamplerNaN (absent "
-                                  "em-matlabbox); out of scope")
+    if not doELBsampling and not doELBsampleAlternate:
+        _refuse_gibbs_on_nan("mcmcVARshadowrateBlockHybrid.m:494")
+    missing = not doELBsampling
+    alternate = bool(doELBsampling and doELBsampleAlternate)
     if IRF1scale is not None:
-        raise NotImplementedError("IRF outputs (doIRF1) are a later row (SURVEY §8f rank 4)")
+        raise NotImplementedError("IRF outputs (doIRF1): use samplers.generateGIRF")
     doPredictiveDensity = bool(fcstNdraws)
     if doPredictiveDensity:
         if fcstNdraws % MCMCdraws != 0:  # :123-126
@@ -166,8 +177,11 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
     ch.set_elb_model(bm.ndxS, bm.actual_block)
     ch.set_elb_slot(0, bm.elbT0, bm.sNaN)
-    if elb_ps and Nproposals:
+    elb_ps = bool(elb_ps and Nproposals and not missing)
+    if elb_ps:
         ch.set_elb_ps(Nproposals, max(1, -(-burn // 2)))  # m >= MCMCburnin * .5 (:435)
+    if missing or alternate:
+        ch.set_elb_treatment(missing=missing, alternate=alternate)  # :481-499 / :470-475
     st = initial_state(m, B)
     ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
     if doPredictiveDensity:
@@ -181,15 +195,16 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     _run_chain_set(ch, burn, MCMCdraws, doprogress)
     if doPredictiveDensity:
         fc = ch.get_fcst(paths=True)
-    if stats is not None and elb_ps and Nproposals:
+    if stats is not None and elb_ps:
         ps = ch.get_ps()
         stats.update(countELBaccept=ps["countAccept"], countELBacceptBurnin=ps["countAcceptBurnin"],
                      stackAccept=ps["stackAccept"])
+    miss = ch.get_missingrate() if (missing or alternate) and bm.elbT else None
     out = ch.get_draws()
     ch.close()
     sr = out.get("shadowrate_all", np.full((MCMCdraws, len(bm.ndxS), 0, B), np.nan))
     res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"], sr,
-           np.full((MCMCdraws, len(bm.ndxS), bm.elbT, B), np.nan)]
+           miss[:, :, :bm.elbT] if miss is not None else np.full((MCMCdraws, len(bm.ndxS), bm.elbT, B), np.nan)]
     if doPredictiveDensity:
         # outputs 7-13 (:692-748): censored draws / mean, uncensored yields (shadow-rate
         # forecasts) / mean, the three one-step score draws
@@ -213,7 +228,9 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
     :397-436), and the linear model's predictive density whose censored recursion floors
     ndxOTHERYIELDS only (:539-546), chain set model CCMM_MODEL_SHADOWRATE.  Outputs 1-17:
     PAI_all, PHI_all, invA_all, sqrtht_all, shadowrate_all, missingrate_all (proposal 1 of the
-    sweep's PS draws, :435, 498; NaN for Gibbs sweeps), fcstYdraws, fcstYhat, fcstYcensorDraws, fcstYcensorHat, fcstShadowrateDraws, fcstShadowrateHat,
+    sweep's PS draws, :435, 498; NaN for Gibbs sweeps; with doELBsampling=False, the missing-data
+    treatment of :442-459, the sweep's one unconstrained draw, which is also the data, and
+    shadowrate_all is NaN), fcstYdraws, fcstYhat, fcstYcensorDraws, fcstYcensorHat, fcstShadowrateDraws, fcstShadowrateHat,
     fcstYhatRB, fcstLogscoreDraws, fcstLogscoreXdraws, fcstLogscoreIdraws, stackAccept
     (:630-700).  Indices 0-based."""
     if check_stationarity:
@@ -221,8 +238,7 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
                                   "all pass 0")
     if doPAIactual:
         raise NotImplementedError("doPAIactual = true (CTA on the actual data, :322-324) is not built")
-    if not doELBsampling:
-        raise NotImplementedError("doELBsampling = false (missing-data treatment) is not built")
+    missing = not doELBsampling
     if IRF1scale is not None:
         raise NotImplementedError("in-sampler IRF outputs: use samplers.generateGIRF")
     doPredictiveDensity = bool(fcstNdraws)
@@ -240,6 +256,9 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
     ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
     ch.set_elb_model(bm.ndxS, None)
     ch.set_elb_slot(0, bm.elbT0, bm.sNaN)
+    if missing:
+        Nproposals = 0
+        ch.set_elb_treatment(missing=True)                    # :442-459
     if Nproposals:
         ch.set_elb_ps(Nproposals, max(1, -(-burn // 2)))      # m >= MCMCburnin * .5 (:403)
         ch.keep_missingrate(True)                             # missingrate = proposal 1 (:435, 498)
@@ -263,7 +282,7 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
         if stats is not None:
             stats.update(countELBaccept=ps["countAccept"], countELBacceptBurnin=ps["countAcceptBurnin"])
     fc = ch.get_fcst(paths=True) if doPredictiveDensity else None
-    miss = ch.get_missingrate() if Nproposals and bm.elbT else None
+    miss = ch.get_missingrate() if (Nproposals or missing) and bm.elbT else None
     out = ch.get_draws()
     ch.close()
     sr = out.get("shadowrate_all", np.full((MCMCdraws, len(bm.ndxS), 0, B), np.nan))
@@ -311,10 +330,9 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
     if check_stationarity:
         import warnings
         warnings.warn("no stationarity check for hybrid model")  # :22-24
-    if not doELBsampling or doELBsampleAlternate:
-        raise NotImplementedError("doELBsampling=false / doELBsampleAlternate=true need the "
-                                  "missing-data sampler VARTVPSVprecisionsamplerNaN (absent "
-                                  "em-matlabbox); out of scope")
+    if not doELBsampling and not doELBsampleAlternate:
+        _refuse_gibbs_on_nan("mcmcVARhybridGibbs.m:513")
+    missing = not doELBsampling  # (doELBsampling=true ignores doELBsampleAlternate: :488-496 is commented out)
     if IRF1scale is not None:
         raise NotImplementedError("in-sampler IRF outputs: use samplers.generateGIRF(hybrid=True)")
     doPredictiveDensity = bool(fcstNdraws)
@@ -337,7 +355,10 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
     ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
     ch.set_elb_model(hm.ndxS, None)
     ch.set_elb_slot(0, hm.elbT0, hm.sNaN)
-    if elb_ps and Nproposals:
+    elb_ps = bool(elb_ps and Nproposals and not missing)
+    if missing:
+        ch.set_elb_treatment(missing=True)             # :499-518
+    if elb_ps:
         ch.set_elb_ps(Nproposals, 1)                   # every sweep (:458)
         ch.keep_missingrate(True)                      # missingrate = proposal 1 (:486)
     N = m.N
@@ -351,12 +372,12 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
     st = initial_state(m, B)
     ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
     _run_chain_set(ch, burn, MCMCdraws, doprogress)
-    if stats is not None and elb_ps and Nproposals:
+    if stats is not None and elb_ps:
         ps = ch.get_ps()
         stats.update(countELBaccept=ps["countAccept"] + ps["countAcceptBurnin"],
                      stackAccept=ps["stackAccept"])
     fc = ch.get_fcst(paths=True) if doPredictiveDensity else None
-    miss = ch.get_missingrate() if elb_ps and Nproposals and hm.elbT else None
+    miss = ch.get_missingrate() if (elb_ps or missing) and hm.elbT else None
     out = ch.get_draws()
     ch.close()
     sr = out.get("shadowrate_all", np.full((MCMCdraws, len(hm.ndxS), 0, B), np.nan))
@@ -682,7 +703,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                                      chunk=50, max_retries=2, keep_draws=False, progress=False,
                                      Nproposals=1000, elb_ps=True, postprocess=False, cumcode=None,
                                      setQuantiles=None, maxlambda=False, model="blockhybrid",
-                                     engine="python"):
+                                     engine="python", doELBsampling=True):
     """The quasi-real-time OOS run of goVARshadowrateBlockHybrid.m:126-517 for the block-
     hybrid shadow-rate VAR, as ONE device-resident chain set per rank: every vintage
     thisT in Tjumpoffs (default: ydates > 2008-12, :127) is a data slot of the set with
@@ -742,9 +763,18 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     engine="native" runs the rank's vintage loop (chain set, burn-in, kept sweeps, forecast
     records, device summaries, retries) inside the library, ccmm_run_batch (include/ccmm.h): the
     same Philox streams and the same per-vintage results (keep_draws / maxlambda not available
-    there)."""
+    there).
+
+    doELBsampling=False (the drivers' "otherwise treats fedfunds as missing data") runs the missing-data
+    treatment per vintage (ccmm_chains_set_elb_treatment): shadowrateVintages* are NaN (:492) and
+    missingrateVintagesMid / Tails summarise the kept draws of the censored cells, for every model.
+    Python engine only: ccmm_batch_config has no field for it."""
     import time
     from . import distributed as dm
+    missing = not doELBsampling
+    if missing and engine == "native":
+        raise ValueError("doELBsampling=False runs on the Python engine (engine='python'): "
+                         "ccmm_batch_config carries no treatment field")
     data0 = np.asarray(data0, float)
     ydates0 = np.asarray(ydates0, float)
     Tdata, N = data0.shape
@@ -811,7 +841,9 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                                           gibbsburn=gibbsburn, ELBbound=ELBbound,
                                           ndxYIELDS=ndxYIELDS, fcstNhorizons=H, Nd=Nd,
                                           keep_paths=dev, model=model)
-        use_ps = bool(elb_ps and Nproposals and ch.elbTmax)
+        use_ps = bool(elb_ps and Nproposals and ch.elbTmax and not missing)
+        if missing:
+            ch.set_elb_treatment(missing=True)
         if use_ps:
             # block hybrid, shadow rate: m >= MCMCburnin * .5 (:435, mcmcVARshadowrate.m:403);
             # hybrid: every sweep (mcmcVARhybridGibbs.m:458)
@@ -834,6 +866,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         P2sum = np.zeros((K, N, B))
         elbTmax = ch.elbTmax
         shadow = np.empty((MCMCdraws, Ns, elbTmax, B)) if elbTmax else None
+        miss = np.empty((MCMCdraws, Ns, elbTmax, B)) if (missing and elbTmax) else None
         PAIdraws = np.empty((MCMCdraws, K, N, B)) if (keep_draws or maxlambda) else None
         post = {}
         done = 0
@@ -842,6 +875,8 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
             ch.sweep(n, store=True)
             if not dev:
                 fc = ch.get_fcst()
+                if miss is not None:
+                    miss[done:done + n] = ch.get_missingrate()
                 dr = ch.get_draws(which={"PAI_all", "shadowrate_all"})
                 scores[:, done:done + n] = fc["scores"]
                 fYsum += fc["fYsum"]
@@ -856,7 +891,6 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
             done += n
             if progress:
                 print(f"[rank {rank}] kept {done}/{MCMCdraws} ({time.perf_counter() - t1:.1f} s)", flush=True)
-        miss = None
         if dev:
             # goVARshadowrateBlockHybrid.m:349-480 on the device, per vintage (data slot)
             for k, i in enumerate(vidx):
@@ -891,7 +925,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
             fYsum[:] = fc["fYsum"]
             fYcsum[:] = fc["fYcsum"]
             yhsum[:] = fc["yhatsum"]
-            if is_sr and use_ps:
+            if (is_sr and use_ps) or (missing and elbTmax):
                 miss = ch.get_missingrate()                                     # M x Ns x elbTmax x B
             dr = ch.get_draws(which={"shadowrate_all"} | ({"PAI_all"} if PAIdraws is not None else set()))
             if shadow is not None:
@@ -951,12 +985,6 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                              fcstYmvlogscoreDraws=scores[:, :, 1, cs].ravel(order="F"),
                              fcstYmvlogscoreXdraws=scores[:, :, 2, cs].ravel(order="F"),
                              fcstYmvlogscoreIdraws=scores[:, :, 3, cs].ravel(order="F"))
-                if miss is not None and bm.elbT > 0:
-                    # missingrate_all permuted to (Nobs, Ns, draws): MATLAB median (NaN if any draw
-                    # is NaN) and prctile (NaN draws removed), goVARshadowrate.m:345-348
-                    mr = miss[:, :, :bm.elbT, cs].transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
-                    r["missingrateMid"] = np.median(mr, axis=2)
-                    r["missingrateTails"] = np.moveaxis(matlab_prctile(mr, [5, 25, 75, 95], axis=2), 0, 2)
             elif i in post:
                 q = post[i]
                 nq = pct.size
@@ -984,6 +1012,12 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                 r["PAImean"] = Psum[:, :, cs].sum(axis=2) / nk
                 var = P2sum[:, :, cs].sum(axis=2) / nk - r["PAImean"] ** 2
                 r["PAIstdev"] = np.sqrt(np.maximum(var, 0.0))               # std(.,1,1): 1/n
+            if miss is not None and bm.elbT > 0:
+                # missingrate_all permuted to (Nobs, Ns, draws): MATLAB median (NaN if any draw
+                # is NaN) and prctile (NaN draws removed), goVARshadowrate.m:345-348
+                mr = miss[:, :, :bm.elbT, cs].transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
+                r["missingrateMid"] = np.median(mr, axis=2)
+                r["missingrateTails"] = np.moveaxis(matlab_prctile(mr, [5, 25, 75, 95], axis=2), 0, 2)
             if shadow is not None and keep_draws:
                 r["shadowrate_all"] = shadow[:, :, :bm.elbT, cs].copy()     # M x Ns x elbT x C
             if shadow is not None:
@@ -1061,6 +1095,9 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     if is_sr:
         out.update(fcstYhatRB=np.full((N, H, V), np.nan), fcstYcensorhat=np.full((N, H, V), np.nan),
                    missingrateVintagesMid=np.full((Tdata, Ns, V), np.nan),
+                   missingrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
+    elif missing:
+        out.update(missingrateVintagesMid=np.full((Tdata, Ns, V), np.nan),
                    missingrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
     if keep_draws:
         out["PAI_all"] = {}

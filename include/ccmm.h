@@ -59,6 +59,7 @@ extern "C" {
 #define CCMM_STATUS_PS_GIBBS 64     /* the PS precision was not positive definite: the Gibbs draw served the
                                        sweep, as the reference's fallback (:462-463) does (valid) */
 #define CCMM_STATUS_INFO (CCMM_STATUS_QR | CCMM_STATUS_PS_GIBBS)  /* informational bits */
+#define CCMM_STATUS_PS 128          /* missing-data / alternate draw: precision not positive definite (invalid draws) */
 
 /* model ids for the sweep-level API */
 #define CCMM_MODEL_LINEAR 0        /* mcmcVAR.m */
@@ -76,6 +77,15 @@ extern "C" {
 #define CCMM_RNG_ELB 6   /* rand(Ns,elbT,101)     gibbsdrawShadowrates.m:173 */
 #define CCMM_RNG_FCST 7  /* randn(N,H*Nd) then randn(N,H,Nd)  mcmcVAR.m:302,306 */
 #define CCMM_RNG_PS 8    /* randn(nmiss,Nproposals)  PS proposals, mcmcVARshadowrateBlockHybrid.m:439-441 */
+#define CCMM_RNG_PSALT 9 /* randn(nmiss,1)        the alternate draw, mcmcVARshadowrateBlockHybrid.m:471-475 */
+
+/* treatment of the months at the ELB (ccmm_chains_set_elb_treatment) */
+#define CCMM_ELB_TREAT_SHADOW 0   /* default: the censored cells are sampled below the bound (Gibbs / PS) */
+#define CCMM_ELB_TREAT_MISSING 1  /* :481-499: one unconstrained draw per sweep becomes the data */
+#define CCMM_ELB_TREAT_MISSING_PAIR 2  /* UNSUPPORTED, for tools/probe_missingdata.py only: as MISSING with the
+                                          draw by the unfused kernel pair (k_ps_chol_w then k_ps_apply) instead
+                                          of k_ps_draw1, same bits.  Not part of the interface: it may change
+                                          or go without a new CCMM_ABI_VERSION */
 
 typedef struct ccmm_ctx ccmm_ctx;
 typedef struct ccmm_chains ccmm_chains;
@@ -393,6 +403,34 @@ int ccmm_chains_set_elb_slot(ccmm_chains* ch, int slot, int elbT0, const uint8_t
  * nproposals) to every sweep's record.  nproposals = 0: Gibbs every sweep (default).
  * Requires Ns (p + 1) <= 80. */
 int ccmm_chains_set_elb_ps(ccmm_chains* ch, int nproposals, int ps_from_m);
+/* Treatment of the ELB months (doELBsampling / doELBsampleAlternate of the reference samplers); call after
+ * ccmm_chains_set_elb_model and before ccmm_chains_set_state.
+ * CCMM_ELB_TREAT_MISSING (doELBsampling = false: mcmcVARshadowrateBlockHybrid.m:481-499,
+ * mcmcVARhybridGibbs.m:499-518, mcmcVARshadowrate.m:442-459; block-hybrid, hybrid and shadow-rate
+ * models): every sweep's ELB step takes one unconstrained draw of the censored cells from the precision
+ * sampler and writes it over them whether or not it lies below the bound; no Gibbs kernel runs.
+ * alternate must be 0, ccmm_chains_set_elb_ps with nproposals > 0 is refused (either call order) and the
+ * censored-cell band width must be <= 80.  The CRN record is the one ccmm_chains_set_elb_ps(ch, 1, .)
+ * gives (the CCMM_RNG_ELB block present and unread, the draw's normals the first nmiss of CCMM_RNG_PS);
+ * under Philox the draw takes the numbers of proposal 1 of a PS sweep.  A precision that is not positive
+ * definite sets CCMM_STATUS_PS and leaves the cells as they were.  Stored sweeps keep shadowrate_all NaN
+ * (:492) and the draw as missingrate (ccmm_chains_get_missingrate; no ccmm_chains_keep_missingrate
+ * call needed); ccmm_chains_get_shadowrate returns the imputed path; the counts of ccmm_chains_get_ps
+ * stay 0.
+ * CCMM_ELB_TREAT_SHADOW with alternate = 1 (doELBsampleAlternate, block hybrid only, :470-475): after the
+ * sweep's ELB step one more unconstrained draw from the same precision and the observed data is stored
+ * as missingrate and enters nothing else; chain state and all other draws are those of the run without
+ * it.  CRN mode appends a block CCMM_RNG_PSALT of Ns elbTmax normals last; Philox uses block id 9 with
+ * the per-cell numbering of CCMM_RNG_PS.  The status word can differ from that run's: where the sweep's own
+ * PS precision is not positive definite (CCMM_STATUS_PS_GIBBS, informational: the Gibbs draw serves the
+ * sweep) the alternate draw factors the same precision, fails too and sets CCMM_STATUS_PS, so a run that is
+ * valid without alternate is reported invalid with it (that sweep's missingrate is then the state's copy,
+ * not a draw). */
+int ccmm_chains_set_elb_treatment(ccmm_chains* ch, int treatment, int alternate);
+/* Host-only: 1 if the one-draw kernel (k_ps_draw1) keeps the band factor of nmax censored cells of band
+ * width W (16, 32, 48 or 64) in LDS over an ELB window of elbTmax months, 0 if it reads it back from
+ * global memory. */
+int ccmm_ps_draw1_resident(int W, int elbTmax, int nmax);
 /* PS bookkeeping (:303-305, 453-460): countAccept / countAcceptBurnin B ints since set_state
  * (sweeps whose proposal was accepted after / during burn-in), stackAccept M x B ints
  * (ndxAccept of each stored draw, 0 = no proposal accepted or Gibbs sweep; M = stored draws;
