@@ -678,7 +678,7 @@ def gibbsdraw_shadowrates(Y, STATE0, YHAT0, ndxS, sNaN, p, C, Psi, SVol, elbBoun
     Cp = np.empty((Nstate, Nstate, p + 1))
     Cp[:, :, 0] = np.eye(Nstate)
     for k in range(p):
-        Cp[:, :, k + 1] = cc @ Cp[:, :, k]
+        Cp[:, :, k + 1] = cc @ np.ascontiguousarray(Cp[:, :, k])  # (a strided operand takes matmul's slow path)
     Cp = Cp[:, :Ny, :]
     # smoothing weights (gibbsdrawShadowrates.m:74-95)
     t = 0
@@ -803,7 +803,7 @@ def gibbsdraw_shadowrates_b3(Y, STATE0, ndxS, sNaN, p, A, B, SVol, elbBound, Ndr
     Ap = np.empty((Nstate, Nstate, p + 1))
     Ap[:, :, 0] = np.eye(Nstate)
     for k in range(p):
-        Ap[:, :, k + 1] = aa @ Ap[:, :, k]
+        Ap[:, :, k + 1] = aa @ np.ascontiguousarray(Ap[:, :, k])
     Ap = Ap[:, :Ny, :]
     t = 0
     for t in range(1, T - p + 1):  # :79-100
