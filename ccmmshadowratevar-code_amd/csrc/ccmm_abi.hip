@@ -1,7 +1,8 @@
 // C-ABI implementation of libccmm (include/ccmm.h): contexts, device-resident
 // chain sets and the block-level drop-ins.  Host code only: the kernels are defined in their own
 // translation units (ccmm_kernels / ccmm_gram_chol / ccmm_cta_solve / ccmm_elb / ccmm_ps / ccmm_fcst /
-// ccmm_lag / ccmm_svpart / ccmm_big / ccmm_bign / ccmm_post / ccmm_girf) and declared in their headers.
+// ccmm_lag / ccmm_svpart / ccmm_big / ccmm_bign / ccmm_post / ccmm_girf), each with the host launchers of its
+// templated kernels; their headers hold the LDS sizes and the launch decisions this file reads.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -221,31 +222,27 @@ static PhaseLock& phase_lock(int device, int id) {
   return *p;
 }
 
-// the predictive-density kernels of one kept draw per chain (ccmm_fcst.hip): the paths (one
-// single-wave workgroup per (draw, chain); job Nd = the linear model's mean path) then the scores
-static void launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt) {
-  const bool reg = fcst_reg_path(a.N, a.p, a.bh) && reg_opt;
-  a.hc = fcst_chunk(a.N, a.Kx, a.p, a.H, reg);
-  a.sv1 = sv1;
-  const size_t lp = fcst_paths_lds_doubles(a.N, a.Kx, a.p, a.hc, reg) * sizeof(double);
-  const size_t ls = fcst_scores_lds_doubles(a.N) * sizeof(double);
-  if (lp > 160 * 1024) throw std::runtime_error("forecast state does not fit LDS");
-  const int njobs = a.bh ? a.Nd : a.Nd + 1;
-  const bool even = reg && a.N % 2 == 0 && a.N < kFcstRegN;
-  const void* kf = even ? (const void*)k_fcst<kFcstRegN - 1>
-                        : reg ? (const void*)k_fcst<kFcstRegN> : (const void*)k_fcst<0>;
-  HIPCHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lp));
-  if (even)
-    hipLaunchKernelGGL(k_fcst<kFcstRegN - 1>, dim3(njobs, a.B), dim3(64), lp, st, a);
-  else if (reg)
-    hipLaunchKernelGGL(k_fcst<kFcstRegN>, dim3(njobs, a.B), dim3(64), lp, st, a);
-  else
-    hipLaunchKernelGGL(k_fcst<0>, dim3(njobs, a.B), dim3(64), lp, st, a);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipFuncSetAttribute((const void*)k_fcst_scores, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls));
-  hipLaunchKernelGGL(k_fcst_scores, dim3(a.Nd, a.B), dim3(64), ls, st, a);
-  HIPCHECK(hipGetLastError());
-}
+// One locked phase of a chain set (id > 0; else a no-op): takes the lock and orders the stream after the
+// latest locked phase; release() records the set's event after this one and publishes it.
+struct PhaseScope {
+  std::unique_lock<std::mutex> lk;
+  PhaseLock* L = nullptr;
+  hipStream_t st;
+  hipEvent_t& ev;
+  PhaseScope(int device, int id, hipStream_t stream, hipEvent_t& event) : st(stream), ev(event) {
+    if (id <= 0) return;
+    L = &phase_lock(device, id);
+    lk = std::unique_lock<std::mutex>(L->m);
+    if (L->last) HIPCHECK(hipStreamWaitEvent(st, L->last, 0));
+    if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  void release() {
+    if (!L) return;
+    HIPCHECK(hipEventRecord(ev, st));
+    L->last = ev;
+    lk.unlock();
+  }
+};
 
 struct ccmm_chains {
   ccmm_ctx* ctx = nullptr;
@@ -596,10 +593,9 @@ struct ccmm_chains {
     lagNT = (N * cfg.p + 15) / 16;
     ldd = (N % 2 == 0) ? N + 1 : N + 2;  // odd stride, spare zero column N
     drows = cfg.T + cfg.p + 4;  // SYRK k-steps read up to row T + p + 2
-    const size_t lds_max = 160 * 1024;
     if (!lag_supported_nt(lagNT) || N > 32 || 16 * lagNT + 1 > d.KP ||
-        gl_lds_bytes(lagNT, drows, ldd, d.TP) > lds_max ||
-        sl_lds_bytes(lagNT, drows, ldd, d.TP, N <= 8 ? 8 : (N <= 20 ? 20 : 32)) > lds_max)
+        gl_lds_bytes(lagNT, drows, ldd, d.TP) > kLdsCu ||
+        sl_lds_bytes(lagNT, drows, ldd, d.TP, n_bucket(N)) > kLdsCu)
       return;
     lag_capable = true;
     Dpool.alloc((size_t)nX * drows * ldd);
@@ -998,26 +994,12 @@ struct ccmm_chains {
     }
     rdiag.alloc((size_t)d.nmat * d.KP);
   }
-  static constexpr int kResidMultiMinB = 16;
   void run_resid() {
-    ChainState cs = view();
-    const int nb = d.N <= 8 ? 8 : (d.N <= 20 ? 20 : 32);
-    const size_t lds = (size_t)d.K * nb * sizeof(double);
-    launch(KID_RESID, [&] {
-      // one pass per design slab (k_resid_multi) once the chains fill the chip; at small B the per-equation
-      // kernel's B N TP / 256 workgroups keep the slab loads in flight (0.12 -> ~0.01 ms at B = 1): the same
-      // fma order per equation, so E is bit-identical either way
-      if (d.N <= 32 && lds <= 64 * 1024 && d.B > kResidMultiMinB) {
-        const dim3 g((d.TP + 255) / 256, d.B);
-        if (nb == 8) hipLaunchKernelGGL(k_resid_multi<8>, g, dim3(256), lds, ctx->stream, d, Tslot.p, xsel(), cs);
-        else if (nb == 20) hipLaunchKernelGGL(k_resid_multi<20>, g, dim3(256), lds, ctx->stream, d, Tslot.p, xsel(), cs);
-        else hipLaunchKernelGGL(k_resid_multi<32>, g, dim3(256), lds, ctx->stream, d, Tslot.p, xsel(), cs);
-      } else {
-        hipLaunchKernelGGL(k_resid, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0, ctx->stream, d,
-                           Tslot.p, xsel(), cs);
-      }
-    });
+    launch(KID_RESID, [&] { HIPCHECK(launch_resid(ctx->stream, d, Tslot.p, xsel(), view())); });
     resid_valid = true;
+  }
+  void run_weights(const ChainState& cs, int sqrt_form) {
+    launch(KID_WEIGHTS, [&] { HIPCHECK(launch_cta_weights(ctx->stream, d, Tslot.p, cs, sqrt_form)); });
   }
 
   void run_cta(const RngArgs& ra) {
@@ -1034,42 +1016,14 @@ struct ccmm_chains {
     }
     // generic design (KP <= 256): the register-tiled fused Gram + Cholesky, then the per-chain solve
     const int fnt = d.KP / 16;
-    launch(KID_WEIGHTS, [&] {
-      hipLaunchKernelGGL(k_cta_weights, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0,
-                         ctx->stream, d, Tslot.p, cs, 1);
-    });
-    const size_t lds = (size_t)std::max(2 * kGcTC * gc_ldz(fnt), (fnt + 1) * 16 * kGcLdp) * sizeof(double);
+    require(gram_chol_supported(fnt), "k_gram_chol: unsupported KP");
+    run_weights(cs, 1);
     launch(KID_GRAMCHOL, [&] {
-      switch (fnt) {
-#define CASE_GC(NT)                                                                           \
-  case NT:                                                                                    \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_gram_chol<NT>,                                \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-    hipLaunchKernelGGL(k_gram_chol<NT>, dim3(d.nmat), dim3(512), lds, ctx->stream, d, Tslot.p, \
-                       xsel(), cs, iVdiag.p, rdiag.p, gc_mode);                               \
-    break;
-        CASE_GC(4)
-        CASE_GC(8)
-        CASE_GC(12)
-        CASE_GC(16)
-#undef CASE_GC
-        default:
-          throw ArgError("k_gram_chol: unsupported KP");
-      }
+      HIPCHECK(launch_gram_chol(fnt, ctx->stream, d, Tslot.p, xsel(), cs, iVdiag.p, rdiag.p, gc_mode));
     });
-    const size_t lds_solve2 =
-        (size_t)(d.TP + 2 * d.KP + 64 * kSolveLd + 2 * d.N * d.N) * sizeof(double);
     join_fcst();  // the previous kept sweep's predictive density reads PAI
     launch(KID_SOLVE, [&] {
-      if (d.N <= 8)
-        hipLaunchKernelGGL(k_cta_solve2<8>, dim3(d.B), dim3(256), lds_solve2, ctx->stream, d,
-                           Tslot.p, iVb.p, xsel(), cs, rdiag.p, ra);
-      else if (d.N <= 20)
-        hipLaunchKernelGGL(k_cta_solve2<20>, dim3(d.B), dim3(256), lds_solve2, ctx->stream, d,
-                           Tslot.p, iVb.p, xsel(), cs, rdiag.p, ra);
-      else
-        hipLaunchKernelGGL(k_cta_solve2<32>, dim3(d.B), dim3(256), lds_solve2, ctx->stream, d,
-                           Tslot.p, iVb.p, xsel(), cs, rdiag.p, ra);
+      HIPCHECK(launch_cta_solve2(ctx->stream, d, Tslot.p, iVb.p, xsel(), cs, rdiag.p, ra));
     });
   }
 
@@ -1112,18 +1066,8 @@ struct ccmm_chains {
   void run_cta_big(const RngArgs& ra, const ChainState& cs) {
     Ubuf.alloc((size_t)d.B * d.N * d.TP);
     Dinv.alloc((size_t)d.nmat * d.KP * 64);
-    std::unique_lock<std::mutex> lk;
-    PhaseLock* L = nullptr;
-    if (mfma_lock > 0) {
-      L = &phase_lock(ctx->device, mfma_lock);
-      lk = std::unique_lock<std::mutex>(L->m);
-      if (L->last) HIPCHECK(hipStreamWaitEvent(ctx->stream, L->last, 0));
-      if (!mfma_ev) HIPCHECK(hipEventCreateWithFlags(&mfma_ev, hipEventDisableTiming));
-    }
-    launch(KID_WEIGHTS, [&] {
-      hipLaunchKernelGGL(k_cta_weights, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0,
-                         ctx->stream, d, Tslot.p, cs, 0);
-    });
+    PhaseScope phase(ctx->device, mfma_lock, ctx->stream, mfma_ev);
+    run_weights(cs, 0);
     launch(KID_GRAMBIG, [&] {
       HIPCHECK(big_launch_cta(ctx->stream, d, Tslot.p, slot.p, iVdiag.p, iVb.p, xsel(), cs, bigGroups.p,
                               nGroups, rdiag.p, ra, Ubuf.p, Dinv.p, 1 & big_mask, colx()));
@@ -1132,11 +1076,7 @@ struct ccmm_chains {
       HIPCHECK(big_launch_cta(ctx->stream, d, Tslot.p, slot.p, iVdiag.p, iVb.p, xsel(), cs, bigGroups.p,
                               nGroups, rdiag.p, ra, Ubuf.p, Dinv.p, 2 & big_mask, colx()));
     });
-    if (L) {
-      HIPCHECK(hipEventRecord(mfma_ev, ctx->stream));
-      L->last = mfma_ev;
-      lk.unlock();
-    }
+    phase.release();
     join_fcst();  // the previous kept sweep's predictive density reads PAI
     launch(KID_SOLVEBIG, [&] {
       HIPCHECK(big_launch_cta(ctx->stream, d, Tslot.p, slot.p, iVdiag.p, iVb.p, xsel(), cs, bigGroups.p,
@@ -1144,20 +1084,23 @@ struct ccmm_chains {
     });
   }
 
+  // The parity exports' common part: weights and k_gram_chol_lag at the current state in LagSel mode `mode`,
+  // every system's record left in G
+  void export_lag_gram(const char* inactive, int mode) {
+    require(lag_active(), inactive);
+    ensure_cta();
+    ChainState cs = view();
+    HIPCHECK(launch_cta_weights(ctx->stream, d, Tslot.p, cs, 1));
+    LagSel ls = lagsel();
+    ls.mode = mode;
+    HIPCHECK(lag_launch_gram(lagNT, ctx->stream, gl_lds_bytes(lagNT, drows, ldd, d.TP), d, Tslot.p, ls, cs, iVdiag.p));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+  }
+
   // Parity export: the lag path's weighted Gram of every (chain, equation) system at the current
   // state, [c b'; b M] (K x K, without the prior), decoded from the kernel's tile slots
   void export_cta_gram(double* out) {
-    require(lag_active(), "ccmm_chains_get_cta_gram: the lag-structured CTA path is not active");
-    ensure_cta();
-    ChainState cs = view();
-    hipLaunchKernelGGL(k_cta_weights, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0, ctx->stream, d,
-                       Tslot.p, cs, 1);
-    HIPCHECK(hipGetLastError());
-    LagSel ls = lagsel();
-    ls.mode = 8;
-    const size_t lds_g = gl_lds_bytes(lagNT, drows, ldd, d.TP);
-    HIPCHECK(lag_launch_gram(lagNT, ctx->stream, lds_g, d, Tslot.p, ls, cs, iVdiag.p));
-    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    export_lag_gram("ccmm_chains_get_cta_gram: the lag-structured CTA path is not active", 8);
     const int NT = lagNT, NTILE = gl_ntile(NT), K = d.K, KL = K - 1;
     std::vector<double> o((size_t)gl_out_len(NT));
     for (int mat = 0; mat < d.nmat; ++mat) {
@@ -1185,16 +1128,7 @@ struct ccmm_chains {
   // state as k_gram_chol_lag writes it (gl_out_len(NT) doubles per system: the factor tiles in
   // slot layout, then [1 / L00, L(1 + a, 0)])
   void export_cta_factor(double* out) {
-    require(lag_active(), "ccmm_chains_get_cta_factor: the lag-structured CTA path is not active");
-    ensure_cta();
-    ChainState cs = view();
-    hipLaunchKernelGGL(k_cta_weights, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0, ctx->stream, d,
-                       Tslot.p, cs, 1);
-    HIPCHECK(hipGetLastError());
-    const LagSel ls = lagsel();
-    const size_t lds_g = gl_lds_bytes(lagNT, drows, ldd, d.TP);
-    HIPCHECK(lag_launch_gram(lagNT, ctx->stream, lds_g, d, Tslot.p, ls, cs, iVdiag.p));
-    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    export_lag_gram("ccmm_chains_get_cta_factor: the lag-structured CTA path is not active", lagsel().mode);
     const size_t n = (size_t)gl_out_len(lagNT);
     for (int mat = 0; mat < d.nmat; ++mat)
       HIPCHECK(hipMemcpy(out + (size_t)mat * n, G.p + (size_t)mat * d.KP * d.KP, n * sizeof(double),
@@ -1209,7 +1143,7 @@ struct ccmm_chains {
     const int o = opt[OPT_SOLVE_SPLIT];
     if (o == 0 || (o < 0 && d.B > kSolveSplitMaxB)) return false;
     if (split_resident < 0) {
-      const int nmax = d.N <= 8 ? 8 : (d.N <= 20 ? 20 : 32);
+      const int nmax = n_bucket(d.N);
       split_resident = lag_solve_resident(lagNT, nmax, sl_lds_bytes(lagNT, drows, ldd, d.TP, nmax), opt[OPT_SOLVE_ASYNC]);
     }
     return 2 * d.B <= split_resident;
@@ -1217,30 +1151,16 @@ struct ccmm_chains {
 
   // CTA on the lag structure: sqrt weights -> Gram + Cholesky + inverse -> sequential solve
   void run_cta_lag(const RngArgs& ra, const ChainState& cs) {
-    launch(KID_WEIGHTS, [&] {
-      hipLaunchKernelGGL(k_cta_weights, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0,
-                         ctx->stream, d, Tslot.p, cs, 1);
-    });
+    run_weights(cs, 1);
     const LagSel ls = lagsel();
     const size_t lds_g = gl_lds_bytes(lagNT, drows, ldd, d.TP);
-    const int nmax = d.N <= 8 ? 8 : (d.N <= 20 ? 20 : 32);
+    const int nmax = n_bucket(d.N);
     const size_t lds_s = sl_lds_bytes(lagNT, drows, ldd, d.TP, nmax);
-    std::unique_lock<std::mutex> lk;
-    PhaseLock* L = nullptr;
-    if (mfma_lock > 0) {  // same phase lock as run_cta_big
-      L = &phase_lock(ctx->device, mfma_lock);
-      lk = std::unique_lock<std::mutex>(L->m);
-      if (L->last) HIPCHECK(hipStreamWaitEvent(ctx->stream, L->last, 0));
-      if (!mfma_ev) HIPCHECK(hipEventCreateWithFlags(&mfma_ev, hipEventDisableTiming));
-    }
+    PhaseScope phase(ctx->device, mfma_lock, ctx->stream, mfma_ev);  // same phase lock as run_cta_big
     launch(KID_GRAMLAG, [&] {
       HIPCHECK(lag_launch_gram(lagNT, ctx->stream, lds_g, d, Tslot.p, ls, cs, iVdiag.p));
     });
-    if (L) {
-      HIPCHECK(hipEventRecord(mfma_ev, ctx->stream));
-      L->last = mfma_ev;
-      lk.unlock();
-    }
+    phase.release();
     SolveXch xc{nullptr, nullptr, 0};
     if (solve_split_ok()) {
       if (!solveFlag.p) {
@@ -1264,21 +1184,6 @@ struct ccmm_chains {
     }
     ChainState cs = view();
     const int N = d.N;
-    const int total = (N - 1) * N * (N + 1) / 6 + N * (N - 1) / 2 + 8;
-    size_t lds = (size_t)(total + N * N) * sizeof(double);
-    // stage the chain's residuals in LDS when they fit (N = 20, T = 750: 138 KB in all)
-    int es_off = -1;
-    const size_t staged = lds + (size_t)N * d.TP * sizeof(double);
-    if (staged <= 160 * 1024) {
-      es_off = total + N * N;
-      lds = staged;
-    }
-    // k_astep_w (wave-parallel factorisations, the default) or the one-thread-per-regression
-    // k_astep (option astep_serial); same draws up to summation order inside the factorisation
-    // (identical update order, fma placement as written)
-    const bool v1 = opt[OPT_ASTEP_SERIAL] != 0;
-    const void* fn = v1 ? (const void*)k_astep : (N <= 20 ? (const void*)k_astep_w<20> : (const void*)k_astep_w<32>);
-    if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (!astepTab.p) {  // the 4 x 4 Gram tiles (ii, A, B) of astep_gram_tiles, largest ii first
       std::vector<int> tab(1, 0);
       for (int ii = N - 1; ii >= 1; --ii)
@@ -1289,15 +1194,7 @@ struct ccmm_chains {
       HIPCHECK(hipMemcpy(astepTab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     launch(KID_ASTEP, [&] {
-      if (v1)
-        hipLaunchKernelGGL(k_astep, dim3(d.B), dim3(256), lds, ctx->stream, d, Tslot.p, cs, ra,
-                           cfg.logy2offset, es_off, astepTab.p);
-      else if (N <= 20)
-        hipLaunchKernelGGL(k_astep_w<20>, dim3(d.B), dim3(512), lds, ctx->stream, d, Tslot.p, cs, ra,
-                           cfg.logy2offset, es_off, astepTab.p);
-      else
-        hipLaunchKernelGGL(k_astep_w<32>, dim3(d.B), dim3(512), lds, ctx->stream, d, Tslot.p, cs, ra,
-                           cfg.logy2offset, es_off, astepTab.p);
+      HIPCHECK(launch_astep(opt[OPT_ASTEP_SERIAL] != 0, ctx->stream, d, Tslot.p, cs, ra, cfg.logy2offset, astepTab.p));
     });
   }
 
@@ -1340,20 +1237,7 @@ struct ccmm_chains {
       hipLaunchKernelGGL(k_phi_gen, dim3((d.N * (d.TP + cfg.dPHI) + 255) / 256, d.B), dim3(256), 0,
                          st, d, Tslot.p, cfg.dPHI, cs, ra);
     }, st);
-    size_t lds = (size_t)(4 * d.N * (d.N + 1)) * sizeof(double);
-    const size_t staged = lds + (size_t)d.N * (d.TP + 1) * sizeof(double);
-    // bit 0: eta staged in LDS; bit 1: then Z in the same region (k_phi)
-    const size_t staged_z = lds + (size_t)d.N * std::max(d.TP + 1, d.TP + cfg.dPHI) * sizeof(double);
-    const int stage_eta = staged_z <= 160 * 1024 ? 3 : (staged <= 160 * 1024 ? 1 : 0);
-    if (stage_eta) {
-      lds = (stage_eta & 2) ? staged_z : staged;
-      if (lds > 64 * 1024)
-        HIPCHECK(hipFuncSetAttribute((const void*)k_phi, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-    }
-    launch(KID_PHI, [&] {
-      hipLaunchKernelGGL(k_phi, dim3(d.B), dim3(256), lds, st, d, Tslot.p, cfg.dPHI, sPHI.p, cs, stage_eta);
-    }, st);
+    launch(KID_PHI, [&] { HIPCHECK(launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs)); }, st);
   }
 
   void run_store() {
@@ -1450,7 +1334,7 @@ struct ccmm_chains {
       }
     }
     require(wmax <= kPsWMax, "PS branch: censored-cell band width exceeds 80 (Ns (p + 1) too large)");
-    psW = wmax <= 16 ? 16 : wmax <= 32 ? 32 : wmax <= 48 ? 48 : wmax <= 64 ? 64 : 80;
+    psW = ps_band_bucket(wmax);
     ps_nmax = nmax;
     const size_t B = cfg.B;
     eEtPS.alloc(B * ET * cfg.N);
@@ -1527,25 +1411,10 @@ struct ccmm_chains {
       HIPCHECK(hipMemcpyAsync(psFirst.p, e.Scur, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     if (fused && psW <= 64) {
       const int ET = std::max(cfg.elbTmax, 1);
-      const int res = ps_draw1_resident(psW, ET, ps_nmax);
-      const size_t lds = ps_draw1_lds_bytes(psW, ET, ps_nmax, res);
-      require(lds <= kPsLdsBudget, "PS branch: cell list does not fit LDS");
-      launch(KID_PSCHOL, [&] {
-        switch (psW) {
-#define CASE_PSD(W)                                                                                              \
-  case W:                                                                                                        \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_ps_draw1<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(k_ps_draw1<W>, dim3(d.B), dim3(64), lds, ctx->stream, d, e, ps, cs, ra, res);             \
-    break;
-          CASE_PSD(16)
-          CASE_PSD(32)
-          CASE_PSD(48)
-          CASE_PSD(64)
-#undef CASE_PSD
-          default:
-            throw ArgError("PS band width");
-        }
-      });
+      require(ps_draw1_lds_bytes(psW, ET, ps_nmax, ps_draw1_resident(psW, ET, ps_nmax)) <= kLdsCu,
+              "PS branch: cell list does not fit LDS");
+      require(ps_supported_w(psW), "PS band width");
+      launch(KID_PSCHOL, [&] { HIPCHECK(launch_ps_draw1(ctx->stream, d, e, ps, cs, ra)); });
     } else {
       run_ps_chol(e, ps);
       run_ps_apply(e, ps, ra, false, false);
@@ -1555,61 +1424,18 @@ struct ccmm_chains {
   }
 
   void run_ps_chol(const ElbDev& e, const PsDev& ps) {
-    ChainState cs = view();
-    // option ps_chol_lds: the first-generation k_ps_chol (LDS window) for every band width (same factor)
-    if (psW <= 64 && !opt[OPT_PS_CHOL_LDS]) {  // register-window factorisation, one wave per chain (k_ps_chol_w)
-      const size_t lds = ps_chol_w_lds_bytes(psW, std::max(cfg.elbTmax, 1), ps_nmax);
-      require(lds <= 160 * 1024, "PS branch: cell list does not fit LDS");
-      launch(KID_PSCHOL, [&] {
-        switch (psW) {
-#define CASE_PSC(W)                                                                                              \
-  case W:                                                                                                        \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_ps_chol_w<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(k_ps_chol_w<W>, dim3(d.B), dim3(64), lds, ctx->stream, d, e, ps, cs);                  \
-    break;
-          CASE_PSC(16)
-          CASE_PSC(32)
-          CASE_PSC(48)
-          CASE_PSC(64)
-#undef CASE_PSC
-          default:
-            throw ArgError("PS band width");
-        }
-      });
-    } else {
-      const size_t lds = (size_t)(psW * psW + 2 * psW) * sizeof(double) + (size_t)ps_nmax * sizeof(int);
-      require(lds <= 160 * 1024, "PS branch: cell list does not fit LDS");
-      launch(KID_PSCHOL, [&] {
-        HIPCHECK(hipFuncSetAttribute((const void*)k_ps_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_ps_chol, dim3(d.B), dim3(128), lds, ctx->stream, d, e, ps, cs);
-      });
-    }
+    // register-window factorisation, one wave per chain (k_ps_chol_w), up to band width 64; option ps_chol_lds:
+    // the first-generation k_ps_chol (LDS window) for every band width (same factor)
+    const bool lds_window = psW > 64 || opt[OPT_PS_CHOL_LDS];
+    require((lds_window ? ps_chol_lds_bytes(psW, ps_nmax) : ps_chol_w_lds_bytes(psW, e.elbTmax, ps_nmax)) <= kLdsCu,
+            "PS branch: cell list does not fit LDS");
+    require(ps_supported_w(psW), "PS band width");
+    launch(KID_PSCHOL, [&] { HIPCHECK(launch_ps_chol(lds_window, ctx->stream, d, e, ps, view())); });
   }
 
   void run_ps_apply(const ElbDev& e, const PsDev& ps, const RngArgs& ra, bool kept, bool prop) {
-    launch(KID_PSPROP, [&] {
-      const dim3 g((ps_np + 255) / 256, d.B);
-      switch (psW) {
-#define CASE_PSW(W)                                                                                   \
-  case W:                                                                                             \
-    if (prop) hipLaunchKernelGGL(k_ps_prop<W>, g, dim3(256), 0, ctx->stream, e, ps, ra);              \
-    if (ps.draw1)                                                                                     \
-      hipLaunchKernelGGL((k_ps_apply<W, true>), dim3(d.B), dim3(64), (size_t)ps_nmax * sizeof(double),  \
-                         ctx->stream, e, ps, ra, 0);                                                    \
-    else                                                                                              \
-      hipLaunchKernelGGL((k_ps_apply<W, false>), dim3(d.B), dim3(64), (size_t)ps_nmax * sizeof(double), \
-                         ctx->stream, e, ps, ra, kept ? 1 : 0);                                         \
-    break;
-        CASE_PSW(16)
-        CASE_PSW(32)
-        CASE_PSW(48)
-        CASE_PSW(64)
-        CASE_PSW(80)
-#undef CASE_PSW
-        default:
-          throw ArgError("PS band width");
-      }
-    });
+    require(ps_supported_w(psW), "PS band width");
+    launch(KID_PSPROP, [&] { HIPCHECK(launch_ps_apply(prop, ctx->stream, d.B, e, ps, ra, kept ? 1 : 0)); });
   }
 
   void run_elb(const RngArgs& ra, bool kept) {
@@ -1623,82 +1449,27 @@ struct ccmm_chains {
       e = elb_view();
       e.ps = 1;
     }
-    const int N = d.N, p = cfg.p, Ns = cfg.Ns, Np = N * p;
-    // Φ staged in LDS when it fits (N = 20, p = 12: 40 KB); N = 120 reads it from e.Phi
-    // and Yb - yhat, Yb too (2 elbTmax N doubles: 52 KB at elbT = 165) when they fit beside it
-    size_t lds_prep = (size_t)(2 + Np + N * (Np + 1)) * sizeof(double);
-    int phi_lds = lds_prep <= 160 * 1024 ? 1 : 0;
-    if (!phi_lds) lds_prep = (size_t)(2 + Np) * sizeof(double);
-    const size_t lds_zy = lds_prep + (size_t)2 * cfg.elbTmax * N * sizeof(double);
-    if (phi_lds && lds_zy <= 160 * 1024) {
-      phi_lds |= 2;
-      lds_prep = lds_zy;
-    }
-    // small batches: the window's residual rows over several workgroups per chain (Yb / Z in LDS)
-    int prep_rows = 0, prep_wg = 1;
-    if ((phi_lds & 2) && d.B < 128) {
-      const int per = std::max(1, 256 / d.B);
-      prep_rows = std::max(16, (cfg.elbTmax + per - 1) / per);
-      prep_wg = (cfg.elbTmax + prep_rows - 1) / prep_rows;
-    }
-    launch(KID_ELBPREP, [&] {
-      HIPCHECK(hipFuncSetAttribute((const void*)k_elb_prep, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_prep));
-      hipLaunchKernelGGL(k_elb_prep, dim3(d.B, prep_wg), dim3(kElbPrepThreads), lds_prep, ctx->stream, d, e, xsel(),
-                         cs, phi_lds, prep_rows);
-    });
-    // W_k of kb lags at once (all p + 1 when they fit beside the rest; k_elb_cond)
-    const size_t lds_cond0 =
-        (size_t)((p + 1) * Ns * N + (1 + 2 * p * Ns) * Ns + 2 * Ns * Ns + N * p * Ns) * sizeof(double);
-    int kb_cond = p + 1;
-    while (kb_cond > 1 && lds_cond0 + (size_t)kb_cond * N * Ns * sizeof(double) > 96 * 1024) --kb_cond;
-    size_t lds_cond = lds_cond0 + (size_t)kb_cond * N * Ns * sizeof(double);
-    const int a_lds = (lds_cond + (size_t)N * N * sizeof(double) <= 64 * 1024) ? 1 : 0;
-    if (a_lds) lds_cond += (size_t)N * N * sizeof(double);
-    // two waves per censored month (BH N = 20: k_elb_cond 1.30 -> 1.13 ms at B = 256); four when the
-    // month's staging fills a CU's LDS (N > 64)
-    const int nth_cond = (N > 64) ? 256 : 128;
-    launch(KID_ELBCOND, [&] {
-      switch (Ns) {
-#define CASE_NSC(NS)                                                                                 \
-  case NS:                                                                                           \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_elb_cond<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 (int)lds_cond));                                                    \
-    hipLaunchKernelGGL(k_elb_cond<NS>, dim3(e.elbTmax, d.B), dim3(nth_cond), lds_cond, ctx->stream, d, e, cs, a_lds, \
-                       kb_cond);                                                                        \
-    break;
-        CASE_NSC(1)
-        CASE_NSC(2)
-        CASE_NSC(3)
-        CASE_NSC(4)
-        CASE_NSC(5)
-#undef CASE_NSC
-        default:
-          throw ArgError("Ns must be in [1, 5]");
-      }
-    });
+    const int N = d.N, p = cfg.p, Ns = cfg.Ns;
+    require(elb_supported_ns(Ns), "Ns must be in [1, 5]");
+    const ElbPrepPlan prep = elb_prep_plan(N, p, cfg.elbTmax, d.B);
+    launch(KID_ELBPREP, [&] { HIPCHECK(launch_elb_prep(ctx->stream, prep, d, e, xsel(), cs)); });
+    const ElbCondPlan cond = elb_cond_plan(N, p, Ns);
+    launch(KID_ELBCOND, [&] { HIPCHECK(launch_elb_cond(ctx->stream, cond, d, e, cs)); });
     // Gibbs passes: elb_waves passes in flight (k_elb_gibbs_wf, bit-identical draws), or the
     // one-wave sequential kernel (option elb_waves = 1)
-    auto gibbs_lds = [&](int w) {  // shadow rates | per pass: uniforms and their elb_ppnd16 | month tables
-      return w == 1 ? (size_t)3 * e.elbTmax * Ns * sizeof(double) + (size_t)e.elbTmax * sizeof(int)
-                    : (size_t)(1 + 2 * w) * e.elbTmax * Ns * sizeof(double) + (size_t)2 * e.elbTmax * sizeof(int) +
-                          (size_t)(2 * w + 1) * sizeof(int);
-    };
-    int W = opt[OPT_ELB_WAVES] <= 1 ? 1 : (opt[OPT_ELB_WAVES] < 8 ? 4 : 8);
-    while (W > 1 && gibbs_lds(W) > 160 * 1024) W = (W == 8) ? 4 : 1;  // long ELB windows
-    const size_t lds_gibbs = gibbs_lds(W);
+    const int W = elb_gibbs_waves(e.elbTmax, Ns, opt[OPT_ELB_WAVES]);
     // eight passes in flight inside one wave (k_elb_gibbs_oct, bit-identical draws): the default;
     // option elb_oct = 0 selects the wave kernels
-    const size_t lds_oct = (size_t)e.elbTmax * Ns * sizeof(double) + (size_t)2 * e.elbTmax * sizeof(int);
     // (the per-chain wave kernels keep shorter months at B < kElbOctMinB: one wave per chain cannot
     // fill the chip there, and a month costs the octet kernel more latency)
     const int elb_oct = opt[OPT_ELB_OCT];
-    const bool use_oct = elb_oct && lds_oct <= 160 * 1024 && (elb_oct == 2 || d.B >= kElbOctMinB);
+    const bool use_oct =
+        elb_oct && elb_oct_lds_bytes(e.elbTmax, Ns) <= kLdsCu && (elb_oct == 2 || d.B >= kElbOctMinB);
+    // (option ps_chol_lds selects k_ps_chol, which only the unfused pair can run)
+    if (elb_missing) run_draw1(ra, e, 1, !draw1_pair && !opt[OPT_PS_CHOL_LDS]);
     // speculative Gibbs step (option elb_spec, small B): the asynchronous wave kernels start beside the PS
     // branch on a stream of their own and stop once it accepts; the draw is kept only for a rejected PS
     // (the reference's order and draws: PS first, the Gibbs draw the fallback, :438-466)
-    // (option ps_chol_lds selects k_ps_chol, which only the unfused pair can run)
-    if (elb_missing) run_draw1(ra, e, 1, !draw1_pair && !opt[OPT_PS_CHOL_LDS]);
     const bool spec = ps && opt[OPT_ELB_SPEC] && d.B <= kElbMpMaxB && !use_oct && W > 1 && opt[OPT_ELB_ASYNC] &&
                       elb_flags == nullptr;
     hipStream_t gst = ctx->stream;
@@ -1723,106 +1494,22 @@ struct ccmm_chains {
     } else if (ps) {
       run_ps(ra, e, kept);
     }
-    if (elb_missing) {
-      // no Gibbs kernel: the draw is the data (:498)
-    } else if (use_oct) {
-      launch(KID_ELBGIBBS, [&] {
-        switch (Ns) {
-#define CASE_NSO(NS)                                                                                           \
-  case NS:                                                                                                     \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_elb_gibbs_oct<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 (int)lds_oct));                                                               \
-    hipLaunchKernelGGL(k_elb_gibbs_oct<NS>, dim3(d.B), dim3(64), lds_oct, gst, d, e, cs, ra);                   \
-    break;
-          CASE_NSO(1)
-          CASE_NSO(2)
-          CASE_NSO(3)
-          CASE_NSO(4)
-          CASE_NSO(5)
-#undef CASE_NSO
-          default:
-            throw ArgError("Ns must be in [1, 5]");
+    if (!elb_missing) {  // (missing-data treatment: no Gibbs kernel, the draw is the data, :498)
+      // the wavefront over 2 or 4 CUs per chain at small B (k_elb_gibbs_mp, bit-identical draws)
+      const int parts = use_oct ? 1 : elb_parts(W);
+      ElbXch xc{nullptr, 0};
+      if (parts > 1) {
+        elbXch.alloc((size_t)d.B * parts * e.elbTmax * Ns * 2);
+        if (elbXchZeroed != elbXch.p) {  // tags start at zero (tags of a launch are >= 2^16)
+          HIPCHECK(hipMemsetAsync(elbXch.p, 0, elbXch.n * sizeof(double), ctx->stream));
+          elbXchZeroed = elbXch.p;
         }
-      }, gst);
-    } else if (elb_parts(W) > 1) {
-      // the wavefront over 2 or 4 CUs per chain (k_elb_gibbs_mp, bit-identical draws)
-      const int parts = elb_parts(W), wpc = 8 / parts;
-      elbXch.alloc((size_t)d.B * parts * e.elbTmax * Ns * 2);
-      if (elbXchZeroed != elbXch.p) {  // tags start at zero (tags of a launch are >= 2^16)
-        HIPCHECK(hipMemsetAsync(elbXch.p, 0, elbXch.n * sizeof(double), ctx->stream));
-        elbXchZeroed = elbXch.p;
+        xc = ElbXch{elbXch.p, ++elb_epoch};
       }
-      const ElbXch xc{elbXch.p, ++elb_epoch};
-      const size_t lds_mp = (size_t)(1 + 2 * wpc) * e.elbTmax * Ns * sizeof(double) +
-                            (size_t)2 * e.elbTmax * sizeof(int) + (size_t)(wpc + 2) * sizeof(int);
-      launch(KID_ELBGIBBS, [&] {
-#define GIBBS_MP(NS, WPC_, PT)                                                                                  \
-  do {                                                                                                        \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_elb_gibbs_mp<NS, WPC_, PT>,                                   \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mp));                   \
-    hipLaunchKernelGGL((k_elb_gibbs_mp<NS, WPC_, PT>), dim3(d.B, PT), dim3(64 * (WPC_ + 2)), lds_mp, gst,       \
-                       d, e, cs, ra, xc);                                                                     \
-  } while (0)
-#define CASE_MP(NS)                    \
-  case NS:                             \
-    if (parts == 2)                    \
-      GIBBS_MP(NS, 4, 2);              \
-    else                               \
-      GIBBS_MP(NS, 2, 4);              \
-    break;
-        switch (Ns) {
-          CASE_MP(1)
-          CASE_MP(2)
-          CASE_MP(3)
-          CASE_MP(4)
-          CASE_MP(5)
-          default:
-            throw ArgError("Ns must be in [1, 5]");
-        }
-#undef CASE_MP
-#undef GIBBS_MP
-      }, gst);
-    } else
-    launch(KID_ELBGIBBS, [&] {
-#define GIBBS_KA(NS, WW, AS)                                                                                \
-  do {                                                                                                      \
-    HIPCHECK(hipFuncSetAttribute((const void*)k_elb_gibbs_wf<NS, WW, AS>,                                   \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gibbs));              \
-    hipLaunchKernelGGL((k_elb_gibbs_wf<NS, WW, AS>), dim3(d.B), dim3(64 * WW), lds_gibbs, gst, d, e,         \
-                       cs, ra);                                                                             \
-  } while (0)
-#define GIBBS_K(NS, WW)            \
-  do {                             \
-    if (opt[OPT_ELB_ASYNC])        \
-      GIBBS_KA(NS, WW, true);      \
-    else                           \
-      GIBBS_KA(NS, WW, false);     \
-  } while (0)
-#define CASE_NS(NS)                                                                            \
-  case NS:                                                                                     \
-    if (W == 1) {                                                                              \
-      HIPCHECK(hipFuncSetAttribute((const void*)k_elb_gibbs<NS>,                               \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gibbs)); \
-      hipLaunchKernelGGL(k_elb_gibbs<NS>, dim3(d.B), dim3(64), lds_gibbs, gst, d, e, cs, ra);         \
-    } else if (W == 4) {                                                                       \
-      GIBBS_K(NS, 4);                                                                          \
-    } else {                                                                                   \
-      GIBBS_K(NS, 8);                                                                          \
-    }                                                                                          \
-    break;
-      switch (Ns) {
-        CASE_NS(1)
-        CASE_NS(2)
-        CASE_NS(3)
-        CASE_NS(4)
-        CASE_NS(5)
-        default:
-          throw ArgError("Ns must be in [1, 5]");
-      }
-#undef CASE_NS
-#undef GIBBS_K
-#undef GIBBS_KA
-    }, gst);
+      const ElbGibbsPlan gibbs{use_oct ? kElbGibbsOct : parts > 1 ? kElbGibbsMp : W > 1 ? kElbGibbsWf : kElbGibbsSeq, W,
+                               opt[OPT_ELB_ASYNC] != 0, parts};
+      launch(KID_ELBGIBBS, [&] { HIPCHECK(launch_elb_gibbs(gst, gibbs, d, e, cs, ra, xc)); }, gst);
+    }
     if (spec) {  // the PS branch beside the Gibbs passes; k_ps_apply posts the decision they wait on
       ElbDev ep = e;
       ep.spec = 0;
@@ -1909,7 +1596,7 @@ struct ccmm_chains {
       fPaths.alloc(B * cap * Nd * HN);
       fPathsC.alloc(B * cap * Nd * HN);
     }
-    require(fcst_paths_lds_doubles(N, cfg.K, p, fcst_chunk(N, cfg.K, p, H)) * sizeof(double) <= 160 * 1024,
+    require(fcst_paths_lds_doubles(N, cfg.K, p, fcst_chunk(N, cfg.K, p, H)) * sizeof(double) <= kLdsCu,
             "forecast state does not fit LDS");
     fSv1.alloc(B * Nd * N);
     have_fcst = true;
@@ -2065,7 +1752,7 @@ struct ccmm_chains {
       hipLaunchKernelGGL(k_fcst_jumpoff, dim3(B), dim3(256), 0, fst, N, cfg.p, N * cfg.p + 1, d.TP,
                          Tslot.p, slot.p, xs.ypool, xs.yidx, fldXj, fXj.p, hybrid ? cfg.Ns : 0,
                          hybrid ? dNdxS.p : nullptr, cfg.elb);
-      launch_fcst(fst, a, fSv1.p, opt[OPT_FCST_REG] != 0);
+      HIPCHECK(launch_fcst(fst, a, fSv1.p, opt[OPT_FCST_REG] != 0));
       hipLaunchKernelGGL(k_fcst_accum, dim3(B), dim3(256), 0, fst, N, H, Nd,
                          cfg.store_capacity, fstored, fY.p, fYc.p, (fcst_bh || hybrid) ? nullptr : fYhat.p, fSc.p,
                          fYsum.p, fYcsum.p, fYhatsum.p, fScStore.p, fKeep ? fPaths.p : nullptr,
@@ -3883,7 +3570,7 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
     for (int i = 0; i < N; ++i) nwx += ndxYields[i] ? 0 : 1;
     require(nwx > 0 && nwx < N, "need at least one macro series and one yield");
     HIPCHECK(hipSetDevice(ctx->device));
-    require(fcst_paths_lds_doubles(N, K, p, fcst_chunk(N, K, p, H)) * sizeof(double) <= 160 * 1024,
+    require(fcst_paths_lds_doubles(N, K, p, fcst_chunk(N, K, p, H)) * sizeof(double) <= kLdsCu,
             "forecast state does not fit LDS");
     static const GLNodes gl = make_gl_nodes();
     auto up = [&](DBuf<double>& d, const double* h, size_t n) {
@@ -3924,7 +3611,7 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
     a.fY = dfY.p; a.fYc = dfYc.p; a.yhat = dyhat.p; a.scores = dsc.p; a.status = dst.p;
     a.gl = gl;
     dsv1.alloc((size_t)B * Nd * N);
-    launch_fcst(ctx->stream, a, dsv1.p, ctx->opt[OPT_FCST_REG] != 0);
+    HIPCHECK(launch_fcst(ctx->stream, a, dsv1.p, ctx->opt[OPT_FCST_REG] != 0));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(fcstY, dfY.p, nout * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(fcstYcensor, dfYc.p, nout * sizeof(double), hipMemcpyDeviceToHost));

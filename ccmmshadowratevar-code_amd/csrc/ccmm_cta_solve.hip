@@ -180,9 +180,15 @@ __global__ __launch_bounds__(256) void k_cta_solve2(Dims d, const int* __restric
   }
 }
 
-// ---------------------------------------------------------------- instantiations launched by ccmm_abi.hip
-template __global__ void k_cta_solve2<8>(Dims, const int*, const double*, XSel, ChainState, const double*, RngArgs);
-template __global__ void k_cta_solve2<20>(Dims, const int*, const double*, XSel, ChainState, const double*, RngArgs);
-template __global__ void k_cta_solve2<32>(Dims, const int*, const double*, XSel, ChainState, const double*, RngArgs);
+// ------------------------------------------------------------------ host launcher
+hipError_t launch_cta_solve2(hipStream_t st, Dims d, const int* Tslot, const double* iVb, XSel xs, ChainState cs,
+                             const double* rdiag, RngArgs ra) {
+  const size_t lds = cta_solve2_lds_bytes(d.N, d.KP, d.TP);
+  switch (n_bucket(d.N)) {
+    case 8: return launch_k(k_cta_solve2<8>, dim3(d.B), dim3(256), lds, false, st, d, Tslot, iVb, xs, cs, rdiag, ra);
+    case 20: return launch_k(k_cta_solve2<20>, dim3(d.B), dim3(256), lds, false, st, d, Tslot, iVb, xs, cs, rdiag, ra);
+    default: return launch_k(k_cta_solve2<32>, dim3(d.B), dim3(256), lds, false, st, d, Tslot, iVb, xs, cs, rdiag, ra);
+  }
+}
 
 }  // namespace ccmm

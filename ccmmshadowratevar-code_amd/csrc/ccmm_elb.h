@@ -1,8 +1,11 @@
-// Device views, record layouts and kernel declarations of the ELB shadow-rate step and its
-// acceptance-sampling branch.  The kernels are defined (and instantiated for every template argument
-// ccmm_abi.hip launches) in their own translation units, ccmm_elb.hip and ccmm_ps.hip; this header is
-// what the host side (ccmm_abi.hip) and the predictive-density kernels see.
+// Device views, record layouts, LDS sizes, launch decisions and host launchers of the ELB shadow-rate step and
+// its acceptance-sampling branch.  The kernels are defined in their own translation units, ccmm_elb.hip and
+// ccmm_ps.hip, each with the launchers that pick (and so instantiate) its template arguments; this header is
+// what the host side (ccmm_abi.hip) and the predictive-density kernels see.  The size and decision functions
+// make no HIP call (tests/launch_plans_main.cpp prints them on the host).
 #pragma once
+#include <algorithm>
+
 #include "ccmm_internal.h"
 
 namespace ccmm {
@@ -106,40 +109,172 @@ struct PsDev {
 
 constexpr int kPsChunk = 64;  // assembled band rows per LDS chunk
 
+// band-width bucket (template argument W) of the largest cell window wmax <= kPsWMax
+inline int ps_band_bucket(int wmax) { return wmax <= 16 ? 16 : wmax <= 32 ? 32 : wmax <= 48 ? 48 : wmax <= 64 ? 64 : 80; }
+inline bool ps_supported_w(int W) { return W == 16 || W == 32 || W == 48 || W == 64 || W == 80; }
+
+// LDS of k_ps_chol: win [W x W] | lv [W] | bb [W] | info [nmax ints]
+inline size_t ps_chol_lds_bytes(int W, int nmax) {
+  return (size_t)(W * W + 2 * W) * sizeof(double) + (size_t)nmax * sizeof(int);
+}
+// LDS of k_ps_chol_w: prow [kPsChunk x W] | pb [kPsChunk] | sL [W] | scens [elbTmax ints] | info [nmax ints]
 __host__ __device__ inline size_t ps_chol_w_lds_bytes(int W, int elbTmax, int nmax) {
   return (size_t)(kPsChunk * W + kPsChunk + W) * sizeof(double) + (size_t)(elbTmax + nmax) * sizeof(int);
 }
+// LDS of k_ps_apply: zl [nmax], the proposal's normals
+inline size_t ps_apply_lds_bytes(int nmax) { return (size_t)nmax * sizeof(double); }
 
-// k_ps_draw1: k_ps_chol_w's LDS, L^-1 b and the draw's normals (nmax doubles each), the cells' shadow-rate
-// offsets (nmax ints) and, when resident, the nmax x W band rows of L
-__host__ __device__ inline size_t ps_draw1_lds_bytes(int W, int elbTmax, int nmax, int resident) {
-  return ps_chol_w_lds_bytes(W, elbTmax, nmax) + (size_t)2 * nmax * sizeof(double) + (size_t)nmax * sizeof(int) +
-         (resident ? (size_t)nmax * W * sizeof(double) : 0);
+// LDS of k_ps_draw1 (byte offsets): k_ps_chol_w's doubles prow | pb | sL, then ybl [nmax] (L^-1 b) | zl [nmax] (the
+// draw's normals) | Ll [nmax x W] (the factor's band rows, when resident) | scens [elbTmax ints] | info [nmax ints]
+// | cellL [nmax ints] (the cells' shadow-rate offsets)
+struct PsDraw1Lds {
+  size_t prow, pb, sL, ybl, zl, Ll, scens, info, cellL, end;
+};
+inline PsDraw1Lds ps_draw1_lds(int W, int elbTmax, int nmax, int resident) {
+  const size_t D = sizeof(double), I = sizeof(int);
+  PsDraw1Lds l{};
+  l.pb = l.prow + (size_t)kPsChunk * W * D;
+  l.sL = l.pb + kPsChunk * D;
+  l.ybl = l.sL + W * D;
+  l.zl = l.ybl + nmax * D;
+  l.Ll = l.zl + nmax * D;
+  l.scens = l.Ll + (resident ? (size_t)nmax * W * D : 0);
+  l.info = l.scens + elbTmax * I;
+  l.cellL = l.info + nmax * I;
+  l.end = l.cellL + nmax * I;
+  return l;
 }
-constexpr size_t kPsLdsBudget = 160 * 1024;
+inline size_t ps_draw1_lds_bytes(int W, int elbTmax, int nmax, int resident) {
+  return ps_draw1_lds(W, elbTmax, nmax, resident).end;
+}
 // whether k_ps_draw1 keeps the factor's band rows in LDS (else it reads them back from PsDev::L)
 inline int ps_draw1_resident(int W, int elbTmax, int nmax) {
-  return ps_draw1_lds_bytes(W, elbTmax, nmax, 1) <= kPsLdsBudget ? 1 : 0;
+  return ps_draw1_lds_bytes(W, elbTmax, nmax, 1) <= kLdsCu ? 1 : 0;
 }
 
-// ---------------------------------------------------------------- kernels (ccmm_elb.hip)
-__global__ void k_elb_prep(Dims d, ElbDev e, XSel xs, ChainState cs, int phi_lds, int rows);
-template <int NS> __global__ void k_elb_cond(Dims d, ElbDev e, ChainState cs, int a_lds, int kb);
-template <int NS> __global__ void k_elb_gibbs(Dims d, ElbDev e, ChainState cs, RngArgs ra);
-template <int NS, int W, bool ASYNC> __global__ void k_elb_gibbs_wf(Dims d, ElbDev e, ChainState cs, RngArgs ra);
-template <int NS, int WPC, int PARTS>
-__global__ void k_elb_gibbs_mp(Dims d, ElbDev e, ChainState cs, RngArgs ra, ElbXch xc);
-template <int NS> __global__ void k_elb_gibbs_oct(Dims d, ElbDev e, ChainState cs, RngArgs ra);
+// ---------------------------------------------------------------- launch decisions of the ELB step
+// k_elb_prep.  LDS: X0 [2 + Np] | sPhi [N x (Np + 1)] (phi_lds bit 0: Phi staged when it fits; N = 20, p = 12:
+// 40 KB; N = 120 reads it from e.Phi) | Z = Yb - yhat [elbTmax x N] | Yb [elbTmax x N] (bit 1: when they fit
+// beside it; 52 KB at elbT = 165).  rows > 0 (small batches, bit 1 set): the window's residual rows over wg
+// workgroups per chain, `rows` rows each
+struct ElbPrepPlan {
+  size_t lds;
+  int phi_lds, rows, wg;
+};
+inline ElbPrepPlan elb_prep_plan(int N, int p, int elbTmax, int B) {
+  const int Np = N * p;
+  ElbPrepPlan pl{(size_t)(2 + Np + N * (Np + 1)) * sizeof(double), 1, 0, 1};
+  if (pl.lds > kLdsCu) pl = ElbPrepPlan{(size_t)(2 + Np) * sizeof(double), 0, 0, 1};
+  const size_t lds_zy = pl.lds + (size_t)2 * elbTmax * N * sizeof(double);
+  if (pl.phi_lds && lds_zy <= kLdsCu) {
+    pl.phi_lds |= 2;
+    pl.lds = lds_zy;
+  }
+  if ((pl.phi_lds & 2) && B < 128) {
+    const int per = std::max(1, 256 / B);
+    pl.rows = std::max(16, (elbTmax + per - 1) / per);
+    pl.wg = (elbTmax + pl.rows - 1) / pl.rows;
+  }
+  return pl;
+}
+
+// k_elb_cond.  LDS: Q [(p + 1) x Ns x N] | gS [(1 + 2 p Ns) x Ns] | Pm [Ns x Ns] | Om [Ns x Ns] | Wl [kb x N x Ns]
+// | PS [N x p x Ns] | Al [N x N] (a_lds).  W_k of kb lags at once: all p + 1 when they fit the budget, a tuning
+// choice that leaves a second workgroup room on the CU; A staged beside them when the whole stays within the
+// default dynamic limit.  Two waves per censored month (BH N = 20: 1.30 -> 1.13 ms at B = 256); four when the
+// month's staging fills a CU's LDS (N > 64)
+constexpr size_t kElbCondLdsBudget = 96 * 1024;
+struct ElbCondPlan {
+  size_t lds;
+  int threads, a_lds, kb;
+};
+inline ElbCondPlan elb_cond_plan(int N, int p, int Ns) {
+  const size_t lds0 = (size_t)((p + 1) * Ns * N + (1 + 2 * p * Ns) * Ns + 2 * Ns * Ns + N * p * Ns) * sizeof(double);
+  const size_t per_lag = (size_t)N * Ns * sizeof(double), lds_a = (size_t)N * N * sizeof(double);
+  int kb = p + 1;
+  while (kb > 1 && lds0 + kb * per_lag > kElbCondLdsBudget) --kb;
+  const size_t lds = lds0 + kb * per_lag;
+  const int a_lds = lds + lds_a <= kLdsDefault ? 1 : 0;
+  return ElbCondPlan{lds + (a_lds ? lds_a : 0), N > 64 ? 256 : 128, a_lds, kb};
+}
+
+// LDS of k_elb_gibbs: Sl | Ul | Zl [elbTmax x Ns each] | Tm [elbTmax ints]
+inline size_t elb_gibbs_lds_bytes(int elbTmax, int Ns) {
+  return (size_t)3 * elbTmax * Ns * sizeof(double) + (size_t)elbTmax * sizeof(int);
+}
+// LDS of the wavefront kernels (byte offsets): Sl [elbTmax x Ns] | Ul [W][elbTmax x Ns] | Zl [W][elbTmax x Ns]
+// | Tm [elbTmax ints] | reach [elbTmax ints] | prog [nprog ints] | one int no kernel reads
+struct ElbWaveLds {
+  size_t Sl, Ul, Zl, Tm, reach, prog, spare, end;
+};
+inline ElbWaveLds elb_wave_lds(int elbTmax, int Ns, int W, int nprog) {
+  const size_t pg = (size_t)elbTmax * Ns * sizeof(double), I = sizeof(int);
+  ElbWaveLds l{};
+  l.Ul = l.Sl + pg;
+  l.Zl = l.Ul + W * pg;
+  l.Tm = l.Zl + W * pg;
+  l.reach = l.Tm + elbTmax * I;
+  l.prog = l.reach + elbTmax * I;
+  l.spare = l.prog + nprog * I;
+  l.end = l.spare + I;
+  return l;
+}
+// k_elb_gibbs_wf<NS, W, ASYNC>: W passes in flight, prog [2][W]
+inline ElbWaveLds elb_wf_lds(int elbTmax, int Ns, int W) { return elb_wave_lds(elbTmax, Ns, W, 2 * W); }
+inline size_t elb_wf_lds_bytes(int elbTmax, int Ns, int W) { return elb_wf_lds(elbTmax, Ns, W).end; }
+// k_elb_gibbs_mp<NS, WPC, PARTS>: WPC drawing waves per part, prog [WPC + 1] (the drawing waves, the importer)
+inline ElbWaveLds elb_mp_lds(int elbTmax, int Ns, int WPC) { return elb_wave_lds(elbTmax, Ns, WPC, WPC + 1); }
+inline size_t elb_mp_lds_bytes(int elbTmax, int Ns, int WPC) { return elb_mp_lds(elbTmax, Ns, WPC).end; }
+// k_elb_gibbs_oct (byte offsets): Sl [elbTmax x Ns] | Tm [elbTmax ints] | reach [elbTmax ints]
+struct ElbOctLds {
+  size_t Sl, Tm, reach, end;
+};
+inline ElbOctLds elb_oct_lds(int elbTmax, int Ns) {
+  ElbOctLds l{};
+  l.Tm = l.Sl + (size_t)elbTmax * Ns * sizeof(double);
+  l.reach = l.Tm + elbTmax * sizeof(int);
+  l.end = l.reach + elbTmax * sizeof(int);
+  return l;
+}
+inline size_t elb_oct_lds_bytes(int elbTmax, int Ns) { return elb_oct_lds(elbTmax, Ns).end; }
+
+// passes in flight of the wave kernels for option elb_waves = want: 1 (the sequential k_elb_gibbs), 4 or 8, and
+// fewer when a long ELB window's passes do not fit the CU's LDS (8 -> 4 -> 1)
+inline int elb_gibbs_waves(int elbTmax, int Ns, int want) {
+  int W = want <= 1 ? 1 : (want < 8 ? 4 : 8);
+  while (W > 1 && elb_wf_lds_bytes(elbTmax, Ns, W) > kLdsCu) W = (W == 8) ? 4 : 1;
+  return W;
+}
+
+// the Gibbs kernel of a sweep (bit-identical draws whichever runs): the one-wave sequential kernel, W passes in
+// flight on W waves (lock-step or with per-wave progress flags), the W = 8 wavefront over `parts` CUs per
+// chain, or eight passes in flight inside one wave
+enum ElbGibbsKernel { kElbGibbsSeq, kElbGibbsWf, kElbGibbsMp, kElbGibbsOct };
+struct ElbGibbsPlan {
+  ElbGibbsKernel kernel;
+  int W;       // wf: 4 or 8
+  bool async;  // wf
+  int parts;   // mp: 2 or 4
+};
+
+// ---------------------------------------------------------------- launchers and kernels (ccmm_elb.hip)
+inline bool elb_supported_ns(int Ns) { return Ns >= 1 && Ns <= kElbNsMax; }
+hipError_t launch_elb_prep(hipStream_t st, const ElbPrepPlan& pl, Dims d, ElbDev e, XSel xs, ChainState cs);
+hipError_t launch_elb_cond(hipStream_t st, const ElbCondPlan& pl, Dims d, ElbDev e, ChainState cs);
+// xc: the granule exchange of kElbGibbsMp (unused otherwise)
+hipError_t launch_elb_gibbs(hipStream_t st, const ElbGibbsPlan& pl, Dims d, ElbDev e, ChainState cs, RngArgs ra,
+                            ElbXch xc);
 __global__ void k_elb_spec_select(ElbDev e, const int* slot, int B);
 __global__ void k_elb_rebuild(Dims d, ElbDev e, XSel xs, ChainState cs, int xslab0, double* dpool, int ldd, int drows,
                               double* dcpool, int dcld, long long dcslab);
 __global__ void k_elb_store(ElbDev e, ChainState cs, double* out, int cap, int m);
-// ---------------------------------------------------------------- kernels (ccmm_ps.hip)
-__global__ void k_ps_chol(Dims d, ElbDev e, PsDev ps, ChainState cs);
-template <int W> __global__ void k_ps_chol_w(Dims d, ElbDev e, PsDev ps, ChainState cs);
-template <int W> __global__ void k_ps_draw1(Dims d, ElbDev e, PsDev ps, ChainState cs, RngArgs ra, int resident);
-template <int W> __global__ void k_ps_prop(ElbDev e, PsDev ps, RngArgs ra);
-template <int W, bool FORCED> __global__ void k_ps_apply(ElbDev e, PsDev ps, RngArgs ra, int kept);
+// ---------------------------------------------------------------- launchers and kernels (ccmm_ps.hip)
+// the fused draw k_ps_draw1<ps.W> (W <= 64)
+hipError_t launch_ps_draw1(hipStream_t st, Dims d, ElbDev e, PsDev ps, ChainState cs, RngArgs ra);
+// k_ps_chol_w<ps.W> (W <= 64; register window, one wave per chain) or, lds_window, k_ps_chol (same factor)
+hipError_t launch_ps_chol(bool lds_window, hipStream_t st, Dims d, ElbDev e, PsDev ps, ChainState cs);
+// prop: k_ps_prop<ps.W> over the ps.NP proposals; then k_ps_apply<ps.W, FORCED = ps.draw1 != 0>
+hipError_t launch_ps_apply(bool prop, hipStream_t st, int B, ElbDev e, PsDev ps, RngArgs ra, int kept);
 __global__ void k_ps_first_store(const double* first, const int* elbT, const int* slot, double* out, int per,
                                  int Ns, int cap, int m);
 __global__ void k_ps_store(const int* flag, int* out, int B, int cap, int m);

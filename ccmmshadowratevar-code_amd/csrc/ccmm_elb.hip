@@ -1543,22 +1543,67 @@ __global__ void k_elb_store(ElbDev e, ChainState cs, double* out, int cap, int m
   for (int q = threadIdx.x; q < per; q += blockDim.x) o[q] = (q / e.Ns < T) ? Sc[q] : __builtin_nan("");
 }
 
-// ---------------------------------------------------------------- instantiations launched by ccmm_abi.hip
-#define CCMM_ELB_INST(NS)                                                                              \
-  template __global__ void k_elb_cond<NS>(Dims, ElbDev, ChainState, int, int);                         \
-  template __global__ void k_elb_gibbs<NS>(Dims, ElbDev, ChainState, RngArgs);                         \
-  template __global__ void k_elb_gibbs_wf<NS, 4, false>(Dims, ElbDev, ChainState, RngArgs);            \
-  template __global__ void k_elb_gibbs_wf<NS, 4, true>(Dims, ElbDev, ChainState, RngArgs);             \
-  template __global__ void k_elb_gibbs_wf<NS, 8, false>(Dims, ElbDev, ChainState, RngArgs);            \
-  template __global__ void k_elb_gibbs_wf<NS, 8, true>(Dims, ElbDev, ChainState, RngArgs);             \
-  template __global__ void k_elb_gibbs_mp<NS, 4, 2>(Dims, ElbDev, ChainState, RngArgs, ElbXch);        \
-  template __global__ void k_elb_gibbs_mp<NS, 2, 4>(Dims, ElbDev, ChainState, RngArgs, ElbXch);        \
-  template __global__ void k_elb_gibbs_oct<NS>(Dims, ElbDev, ChainState, RngArgs);
-CCMM_ELB_INST(1)
-CCMM_ELB_INST(2)
-CCMM_ELB_INST(3)
-CCMM_ELB_INST(4)
-CCMM_ELB_INST(5)
-#undef CCMM_ELB_INST
+// ------------------------------------------------------------------ host launchers
+hipError_t launch_elb_prep(hipStream_t st, const ElbPrepPlan& pl, Dims d, ElbDev e, XSel xs, ChainState cs) {
+  return launch_k(k_elb_prep, dim3(d.B, pl.wg), dim3(kElbPrepThreads), pl.lds, true, st, d, e, xs, cs, pl.phi_lds,
+                  pl.rows);
+}
+
+// NS = e.Ns of every templated kernel below; F::run<NS>(...) does the launch
+template <class F, class... A>
+static hipError_t for_ns(int Ns, A... a) {
+  switch (Ns) {
+    case 1: return F::template run<1>(a...);
+    case 2: return F::template run<2>(a...);
+    case 3: return F::template run<3>(a...);
+    case 4: return F::template run<4>(a...);
+    case 5: return F::template run<5>(a...);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+struct CondLaunch {
+  template <int NS>
+  static hipError_t run(hipStream_t st, const ElbCondPlan& pl, Dims d, ElbDev e, ChainState cs) {
+    return launch_k(k_elb_cond<NS>, dim3(e.elbTmax, d.B), dim3(pl.threads), pl.lds, true, st, d, e, cs, pl.a_lds, pl.kb);
+  }
+};
+hipError_t launch_elb_cond(hipStream_t st, const ElbCondPlan& pl, Dims d, ElbDev e, ChainState cs) {
+  return for_ns<CondLaunch>(e.Ns, st, pl, d, e, cs);
+}
+
+struct GibbsLaunch {
+  template <int NS, int W>
+  static hipError_t wf(hipStream_t st, bool async, Dims d, ElbDev e, ChainState cs, RngArgs ra) {
+    const size_t lds = elb_wf_lds_bytes(e.elbTmax, NS, W);
+    return async ? launch_k(k_elb_gibbs_wf<NS, W, true>, dim3(d.B), dim3(64 * W), lds, true, st, d, e, cs, ra)
+                 : launch_k(k_elb_gibbs_wf<NS, W, false>, dim3(d.B), dim3(64 * W), lds, true, st, d, e, cs, ra);
+  }
+  template <int NS, int WPC, int PARTS>
+  static hipError_t mp(hipStream_t st, Dims d, ElbDev e, ChainState cs, RngArgs ra, ElbXch xc) {
+    return launch_k(k_elb_gibbs_mp<NS, WPC, PARTS>, dim3(d.B, PARTS), dim3(64 * (WPC + 2)),
+                    elb_mp_lds_bytes(e.elbTmax, NS, WPC), true, st, d, e, cs, ra, xc);
+  }
+  template <int NS>
+  static hipError_t run(hipStream_t st, const ElbGibbsPlan& pl, Dims d, ElbDev e, ChainState cs, RngArgs ra,
+                        ElbXch xc) {
+    switch (pl.kernel) {
+      case kElbGibbsOct:
+        return launch_k(k_elb_gibbs_oct<NS>, dim3(d.B), dim3(64), elb_oct_lds_bytes(e.elbTmax, NS), true, st, d, e, cs,
+                        ra);
+      case kElbGibbsMp:
+        return pl.parts == 2 ? mp<NS, 4, 2>(st, d, e, cs, ra, xc) : mp<NS, 2, 4>(st, d, e, cs, ra, xc);
+      case kElbGibbsWf:
+        return pl.W == 4 ? wf<NS, 4>(st, pl.async, d, e, cs, ra) : wf<NS, 8>(st, pl.async, d, e, cs, ra);
+      default:
+        return launch_k(k_elb_gibbs<NS>, dim3(d.B), dim3(64), elb_gibbs_lds_bytes(e.elbTmax, NS), true, st, d, e, cs,
+                        ra);
+    }
+  }
+};
+hipError_t launch_elb_gibbs(hipStream_t st, const ElbGibbsPlan& pl, Dims d, ElbDev e, ChainState cs, RngArgs ra,
+                            ElbXch xc) {
+  return for_ns<GibbsLaunch>(e.Ns, st, pl, d, e, cs, ra, xc);
+}
 
 }  // namespace ccmm

@@ -1,5 +1,5 @@
-// Arguments, LDS budgets and kernel declarations of the predictive-density kernels (defined and
-// instantiated in their own translation unit, ccmm_fcst.hip; launched by ccmm_abi.hip).
+// Arguments, LDS budgets, the host launcher and kernel declarations of the predictive-density kernels (their
+// own translation unit, ccmm_fcst.hip).  The size and decision functions make no HIP call.
 #pragma once
 #include <algorithm>
 
@@ -81,12 +81,13 @@ __host__ __device__ inline size_t fcst_scores_lds_doubles(int N) {
 // (the register path: at most 16 horizons, so that eight workgroups share a CU)
 inline int fcst_chunk(int N, int Kx, int p, int H, bool reg = false) {
   int hc = reg ? std::min(H, 16) : H;
-  while (hc > 1 && fcst_paths_lds_doubles(N, Kx, p, hc, reg) * sizeof(double) > 160 * 1024) hc = (hc + 1) / 2;
+  while (hc > 1 && fcst_paths_lds_doubles(N, Kx, p, hc, reg) * sizeof(double) > kLdsCu) hc = (hc + 1) / 2;
   return hc;
 }
 
-template <int RN> __global__ void k_fcst(FcstArgs a);
-__global__ void k_fcst_scores(FcstArgs a);
+// k_fcst<RN> then k_fcst_scores of one kept draw per chain; sets a.hc and a.sv1.  reg_opt: option fcst_reg.
+// Throws std::runtime_error when the paths' state does not fit one CU's LDS
+hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt);
 __global__ void k_fcst_jumpoff(int N, int p, int K, int TP, const int* __restrict__ Tslot,
                                const int* __restrict__ slot, const double* __restrict__ ypool,
                                const int* __restrict__ yidx, int ldXj, double* __restrict__ Xj, int Ns,

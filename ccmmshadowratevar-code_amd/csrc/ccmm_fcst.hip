@@ -10,6 +10,8 @@
 // side of the simulation formed ahead of the recursion in chunks of horizons.  k_fcst_scores: the
 // four one-step log scores of each draw, one single-wave workgroup per (draw, chain), over an
 // N x N LDS scratch (N <= 32): ~N^3 flop per draw.
+#include <stdexcept>
+
 #include "ccmm_fcst.h"
 
 namespace ccmm {
@@ -700,9 +702,22 @@ __global__ void k_fcst_accum(int N, int H, int Nd, int cap, int m, const double*
 }
 
 
-// ---------------------------------------------------------------- instantiations launched by ccmm_abi.hip
-template __global__ void k_fcst<0>(FcstArgs);
-template __global__ void k_fcst<kFcstRegN - 1>(FcstArgs);
-template __global__ void k_fcst<kFcstRegN>(FcstArgs);
+// ------------------------------------------------------------------ host launcher
+// the paths (one single-wave workgroup per (draw, chain); job Nd = the linear model's mean path) then the scores
+hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt) {
+  const bool reg = fcst_reg_path(a.N, a.p, a.bh) && reg_opt;
+  a.hc = fcst_chunk(a.N, a.Kx, a.p, a.H, reg);
+  a.sv1 = sv1;
+  const size_t lp = fcst_paths_lds_doubles(a.N, a.Kx, a.p, a.hc, reg) * sizeof(double);
+  const size_t ls = fcst_scores_lds_doubles(a.N) * sizeof(double);
+  if (lp > kLdsCu) throw std::runtime_error("forecast state does not fit LDS");
+  const dim3 g(a.bh ? a.Nd : a.Nd + 1, a.B);
+  const bool even = reg && a.N % 2 == 0 && a.N < kFcstRegN;
+  const hipError_t e = even  ? launch_k(k_fcst<kFcstRegN - 1>, g, dim3(64), lp, true, st, a)
+                       : reg ? launch_k(k_fcst<kFcstRegN>, g, dim3(64), lp, true, st, a)
+                             : launch_k(k_fcst<0>, g, dim3(64), lp, true, st, a);
+  if (e != hipSuccess) return e;
+  return launch_k(k_fcst_scores, dim3(a.Nd, a.B), dim3(64), ls, true, st, a);
+}
 
 }  // namespace ccmm

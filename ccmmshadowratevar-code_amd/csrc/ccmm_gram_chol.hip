@@ -269,10 +269,25 @@ __global__ __launch_bounds__(512, 1) void k_gram_chol(Dims d, const int* __restr
   if (bad && (tid & 63) == 0) atomicOr(&cs.status[c], 2);
 }
 
-// ---------------------------------------------------------------- instantiations launched by ccmm_abi.hip
-template __global__ void k_gram_chol<4>(Dims, const int*, XSel, ChainState, const double*, double*, int);
-template __global__ void k_gram_chol<8>(Dims, const int*, XSel, ChainState, const double*, double*, int);
-template __global__ void k_gram_chol<12>(Dims, const int*, XSel, ChainState, const double*, double*, int);
-template __global__ void k_gram_chol<16>(Dims, const int*, XSel, ChainState, const double*, double*, int);
+// ------------------------------------------------------------------ host launcher
+bool gram_chol_supported(int NT) { return NT == 4 || NT == 8 || NT == 12 || NT == 16; }
+
+template <int NT>
+static hipError_t gram_chol_nt(hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs, const double* iVdiag,
+                               double* rdiag, int mode) {
+  return launch_k(k_gram_chol<NT>, dim3(d.nmat), dim3(512), gram_chol_lds_bytes(NT), true, st, d, Tslot, xs, cs, iVdiag,
+                  rdiag, mode);
+}
+
+hipError_t launch_gram_chol(int NT, hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs,
+                            const double* iVdiag, double* rdiag, int mode) {
+  switch (NT) {
+    case 4: return gram_chol_nt<4>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
+    case 8: return gram_chol_nt<8>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
+    case 12: return gram_chol_nt<12>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
+    case 16: return gram_chol_nt<16>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
+    default: return hipErrorInvalidValue;
+  }
+}
 
 }  // namespace ccmm

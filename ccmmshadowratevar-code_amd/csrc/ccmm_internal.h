@@ -14,6 +14,25 @@ constexpr int kCholNB = 32;   // Cholesky panel width
 constexpr int kMaxNSmall = 32;  // per-chain small-matrix kernels (A, SV, PHI) support N <= 32
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// template bucket of the per-chain kernels that hold N-vectors in registers (NMAX / NB = 8, 20, 32)
+__host__ __device__ constexpr int n_bucket(int N) { return N <= 8 ? 8 : (N <= 20 ? 20 : 32); }
+
+// ---------------------------------------------------------------- LDS
+constexpr size_t kLdsCu = 160 * 1024;      // LDS of one CU (gfx950): the most one workgroup can take
+constexpr size_t kLdsDefault = 64 * 1024;  // dynamic LDS of a launch without hipFuncAttributeMaxDynamicSharedMemorySize
+
+#ifdef __HIPCC__
+// one launch of kernel k with `lds` bytes of dynamic LDS; raise: lift the kernel's dynamic-LDS limit first
+template <class K, class... A>
+inline hipError_t launch_k(K k, dim3 grid, dim3 block, size_t lds, bool raise, hipStream_t st, A... a) {
+  if (raise) {
+    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k, grid, block, lds, st, a...);
+  return hipGetLastError();
+}
+#endif
 
 // ---------------------------------------------------------------- RNG
 // Philox4x32-10 (Salmon et al. 2011), counter = (pair index, chain, sweep, block),

@@ -839,11 +839,40 @@ __global__ void k_mfma_selftest_acc(const double* A, const double* B, const doub
   for (int r = 0; r < 4; ++r) D[((l >> 4) + 4 * r) + 16 * (l & 15)] = acc[r];
 }
 
-// ---------------------------------------------------------------- instantiations launched by ccmm_abi.hip
-template __global__ void k_resid_multi<8>(Dims, const int*, XSel, ChainState);
-template __global__ void k_resid_multi<20>(Dims, const int*, XSel, ChainState);
-template __global__ void k_resid_multi<32>(Dims, const int*, XSel, ChainState);
-template __global__ void k_astep_w<20>(Dims, const int*, ChainState, RngArgs, double, int, const int*);
-template __global__ void k_astep_w<32>(Dims, const int*, ChainState, RngArgs, double, int, const int*);
+// ------------------------------------------------------------------ host launchers
+hipError_t launch_resid(hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs) {
+  if (!resid_multi(d.N, d.K, d.B))
+    return launch_k(k_resid, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0, false, st, d, Tslot, xs, cs);
+  const dim3 g((d.TP + 255) / 256, d.B);
+  const size_t lds = resid_multi_lds_bytes(d.N, d.K);
+  switch (n_bucket(d.N)) {
+    case 8: return launch_k(k_resid_multi<8>, g, dim3(256), lds, false, st, d, Tslot, xs, cs);
+    case 20: return launch_k(k_resid_multi<20>, g, dim3(256), lds, false, st, d, Tslot, xs, cs);
+    default: return launch_k(k_resid_multi<32>, g, dim3(256), lds, false, st, d, Tslot, xs, cs);
+  }
+}
+
+hipError_t launch_cta_weights(hipStream_t st, Dims d, const int* Tslot, ChainState cs, int sqrt_form) {
+  return launch_k(k_cta_weights, dim3((d.TP + 255) / 256, d.N, d.B), dim3(256), 0, false, st, d, Tslot, cs, sqrt_form);
+}
+
+hipError_t launch_astep(bool serial, hipStream_t st, Dims d, const int* Tslot, ChainState cs, RngArgs ra,
+                        double logy2offset, const int* gtab) {
+  const AstepPlan pl = astep_plan(d.N, d.TP);
+  const bool raise = pl.lds > kLdsDefault;
+  if (serial)
+    return launch_k(k_astep, dim3(d.B), dim3(256), pl.lds, raise, st, d, Tslot, cs, ra, logy2offset, pl.es_off, gtab);
+  if (d.N <= 20)
+    return launch_k(k_astep_w<20>, dim3(d.B), dim3(512), pl.lds, raise, st, d, Tslot, cs, ra, logy2offset, pl.es_off,
+                    gtab);
+  return launch_k(k_astep_w<32>, dim3(d.B), dim3(512), pl.lds, raise, st, d, Tslot, cs, ra, logy2offset, pl.es_off,
+                  gtab);
+}
+
+hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs) {
+  const PhiPlan pl = phi_plan(d.N, d.TP, dPHI);
+  return launch_k(k_phi, dim3(d.B), dim3(256), pl.lds, pl.lds > kLdsDefault, st, d, Tslot, dPHI, sPHIall, cs,
+                  pl.stage_eta);
+}
 
 }  // namespace ccmm

@@ -523,26 +523,52 @@ __global__ void k_ps_store(const int* flag, int* out, int B, int cap, int m) {
   if (c < B) out[(size_t)c * cap + m] = flag ? flag[c] : 0;
 }
 
-// ---------------------------------------------------------------- instantiations launched by ccmm_abi.hip
-template __global__ void k_ps_chol_w<16>(Dims, ElbDev, PsDev, ChainState);
-template __global__ void k_ps_chol_w<32>(Dims, ElbDev, PsDev, ChainState);
-template __global__ void k_ps_chol_w<48>(Dims, ElbDev, PsDev, ChainState);
-template __global__ void k_ps_chol_w<64>(Dims, ElbDev, PsDev, ChainState);
-#define CCMM_PS_INST(W)                                                 \
-  template __global__ void k_ps_prop<W>(ElbDev, PsDev, RngArgs);        \
-  template __global__ void k_ps_apply<W, false>(ElbDev, PsDev, RngArgs, int);  \
-  template __global__ void k_ps_apply<W, true>(ElbDev, PsDev, RngArgs, int);
-#define CCMM_PS_DRAW1(W) template __global__ void k_ps_draw1<W>(Dims, ElbDev, PsDev, ChainState, RngArgs, int);
-CCMM_PS_DRAW1(16)
-CCMM_PS_DRAW1(32)
-CCMM_PS_DRAW1(48)
-CCMM_PS_DRAW1(64)
-#undef CCMM_PS_DRAW1
-CCMM_PS_INST(16)
-CCMM_PS_INST(32)
-CCMM_PS_INST(48)
-CCMM_PS_INST(64)
-CCMM_PS_INST(80)
-#undef CCMM_PS_INST
+// ------------------------------------------------------------------ host launchers
+hipError_t launch_ps_draw1(hipStream_t st, Dims d, ElbDev e, PsDev ps, ChainState cs, RngArgs ra) {
+  const int res = ps_draw1_resident(ps.W, e.elbTmax, ps.nmax);
+  const size_t lds = ps_draw1_lds_bytes(ps.W, e.elbTmax, ps.nmax, res);
+  switch (ps.W) {
+    case 16: return launch_k(k_ps_draw1<16>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs, ra, res);
+    case 32: return launch_k(k_ps_draw1<32>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs, ra, res);
+    case 48: return launch_k(k_ps_draw1<48>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs, ra, res);
+    case 64: return launch_k(k_ps_draw1<64>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs, ra, res);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_ps_chol(bool lds_window, hipStream_t st, Dims d, ElbDev e, PsDev ps, ChainState cs) {
+  if (lds_window)
+    return launch_k(k_ps_chol, dim3(d.B), dim3(128), ps_chol_lds_bytes(ps.W, ps.nmax), true, st, d, e, ps, cs);
+  const size_t lds = ps_chol_w_lds_bytes(ps.W, e.elbTmax, ps.nmax);
+  switch (ps.W) {
+    case 16: return launch_k(k_ps_chol_w<16>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs);
+    case 32: return launch_k(k_ps_chol_w<32>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs);
+    case 48: return launch_k(k_ps_chol_w<48>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs);
+    case 64: return launch_k(k_ps_chol_w<64>, dim3(d.B), dim3(64), lds, true, st, d, e, ps, cs);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <int W>
+static hipError_t ps_apply_w(bool prop, hipStream_t st, int B, ElbDev e, PsDev ps, RngArgs ra, int kept) {
+  if (prop) {
+    const hipError_t err = launch_k(k_ps_prop<W>, dim3((ps.NP + 255) / 256, B), dim3(256), 0, false, st, e, ps, ra);
+    if (err != hipSuccess) return err;
+  }
+  const size_t lds = ps_apply_lds_bytes(ps.nmax);
+  return ps.draw1 ? launch_k(k_ps_apply<W, true>, dim3(B), dim3(64), lds, false, st, e, ps, ra, 0)
+                  : launch_k(k_ps_apply<W, false>, dim3(B), dim3(64), lds, false, st, e, ps, ra, kept);
+}
+
+hipError_t launch_ps_apply(bool prop, hipStream_t st, int B, ElbDev e, PsDev ps, RngArgs ra, int kept) {
+  switch (ps.W) {
+    case 16: return ps_apply_w<16>(prop, st, B, e, ps, ra, kept);
+    case 32: return ps_apply_w<32>(prop, st, B, e, ps, ra, kept);
+    case 48: return ps_apply_w<48>(prop, st, B, e, ps, ra, kept);
+    case 64: return ps_apply_w<64>(prop, st, B, e, ps, ra, kept);
+    case 80: return ps_apply_w<80>(prop, st, B, e, ps, ra, kept);
+    default: return hipErrorInvalidValue;
+  }
+}
 
 }  // namespace ccmm

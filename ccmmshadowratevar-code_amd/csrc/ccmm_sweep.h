@@ -1,8 +1,11 @@
-// Kernel declarations and host-visible layouts of the per-sweep kernels of the generic (small-N) path:
-// residuals, CTA weights, the A-step, the KSC indicators, PHI, the draw store and the drop-in helpers
-// (ccmm_kernels.hip), the fused Gram + Cholesky (ccmm_gram_chol.hip) and the per-chain solve
-// (ccmm_cta_solve.hip).  Each file is its own translation unit; ccmm_abi.hip launches the kernels.
+// Host-visible layouts, LDS sizes, launch decisions and host launchers of the per-sweep kernels of the
+// generic (small-N) path: residuals, CTA weights, the A-step, the KSC indicators, PHI, the draw store and the
+// drop-in helpers (ccmm_kernels.hip), the fused Gram + Cholesky (ccmm_gram_chol.hip) and the per-chain solve
+// (ccmm_cta_solve.hip).  Each file is its own translation unit and launches its own templated kernels; the
+// size and decision functions make no HIP call (tests/launch_plans_main.cpp prints them on the host).
 #pragma once
+#include <algorithm>
+
 #include "ccmm_internal.h"
 
 namespace ccmm {
@@ -45,15 +48,23 @@ struct GcArgs {
              // update, 8 no panel solve, 16 no diagonal factor
 };
 
-template <int NT>
-__global__ void k_gram_chol(Dims d, const int* __restrict__ Tslot, XSel xs, ChainState cs,
-                            const double* __restrict__ iVdiag, double* __restrict__ rdiag, int mode);
+// LDS of k_gram_chol<NT>: max(SYRK stage Z0 | Z1 [kGcTC x gc_ldz(NT)], factor stage Dg | Pn[NT] [16 x kGcLdp])
+inline size_t gram_chol_lds_bytes(int NT) {
+  return (size_t)std::max(2 * kGcTC * gc_ldz(NT), (NT + 1) * 16 * kGcLdp) * sizeof(double);
+}
+bool gram_chol_supported(int NT);  // tile counts KP / 16 with a compiled kernel
+hipError_t launch_gram_chol(int NT, hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs,
+                            const double* iVdiag, double* rdiag, int mode);
 
 // ---------------------------------------------------------------- ccmm_cta_solve.hip
 constexpr int kSolveLd = 65;  // LDS row stride of the staged 64x64 diagonal block
-template <int NMAX>
-__global__ void k_cta_solve2(Dims d, const int* __restrict__ Tslot, const double* __restrict__ iVb, XSel xs,
-                             ChainState cs, const double* __restrict__ rdiag, RngArgs ra);
+// LDS of k_cta_solve2: v [TP] | yv [KP] | rdl [KP] | Ls [64 x kSolveLd] | Al [N x N] | Ael [N x N]
+inline size_t cta_solve2_lds_bytes(int N, int KP, int TP) {
+  return (size_t)(TP + 2 * KP + 64 * kSolveLd + 2 * N * N) * sizeof(double);
+}
+// k_cta_solve2<n_bucket(N)>, one workgroup per chain
+hipError_t launch_cta_solve2(hipStream_t st, Dims d, const int* Tslot, const double* iVb, XSel xs, ChainState cs,
+                             const double* rdiag, RngArgs ra);
 
 // ---------------------------------------------------------------- ccmm_kernels.hip
 // draw storage
@@ -65,18 +76,51 @@ struct Store {
   int cap, m, Tmax;
 };
 
-__global__ void k_resid(Dims d, const int* __restrict__ Tslot, XSel xs, ChainState cs);
-template <int NB> __global__ void k_resid_multi(Dims d, const int* __restrict__ Tslot, XSel xs, ChainState cs);
-__global__ void k_cta_weights(Dims d, const int* __restrict__ Tslot, ChainState cs, int sqrt_form);
-__global__ void k_astep(Dims d, const int* __restrict__ Tslot, ChainState cs, RngArgs ra, double logy2offset,
-                        int es_off, const int* __restrict__ gtab);
-template <int NN>
-__global__ void k_astep_w(Dims d, const int* __restrict__ Tslot, ChainState cs, RngArgs ra, double logy2offset,
-                          int es_off, const int* __restrict__ gtab);
+// one pass per design slab (k_resid_multi<n_bucket(N)>, LDS: PAI rows [K x NB]) once the chains fill the chip;
+// at small B the per-equation k_resid's B N TP / 256 workgroups keep the slab loads in flight (0.12 -> ~0.01 ms
+// at B = 1): the same fma order per equation, so E is bit-identical either way
+constexpr int kResidMultiMinB = 16;
+inline size_t resid_multi_lds_bytes(int N, int K) { return (size_t)K * n_bucket(N) * sizeof(double); }
+inline bool resid_multi(int N, int K, int B) {
+  return N <= 32 && resid_multi_lds_bytes(N, K) <= kLdsDefault && B > kResidMultiMinB;
+}
+hipError_t launch_resid(hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs);
+hipError_t launch_cta_weights(hipStream_t st, Dims d, const int* Tslot, ChainState cs, int sqrt_form);
+
+// LDS of k_astep / k_astep_w: regression blocks ii = 1..N-1 [ii (ii + 1) / 2 + ii] | Anew [N x N] | 8 doubles of
+// slack | E [N x TP] at es_off when the chain's residuals fit beside them (N = 20, T = 750: 138 KB in all), else
+// es_off = -1 and the kernel reads E from global memory
+struct AstepPlan {
+  size_t lds;
+  int es_off;
+};
+inline AstepPlan astep_plan(int N, int TP) {
+  const int total = (N - 1) * N * (N + 1) / 6 + N * (N - 1) / 2 + 8;
+  const size_t lds = (size_t)(total + N * N) * sizeof(double);
+  const size_t staged = lds + (size_t)N * TP * sizeof(double);
+  return staged <= kLdsCu ? AstepPlan{staged, total + N * N} : AstepPlan{lds, -1};
+}
+// k_astep_w<20 / 32> (wave-parallel factorisations) or, serial, the one-thread-per-regression k_astep; same
+// draws up to summation order inside the factorisation (identical update order, fma placement as written)
+hipError_t launch_astep(bool serial, hipStream_t st, Dims d, const int* Tslot, ChainState cs, RngArgs ra,
+                        double logy2offset, const int* gtab);
+
+// LDS of k_phi: Lpost | Rz | Sq | Ph [N x (N + 1) each] | eta [N x (TP + 1)] (stage_eta bit 0), the region wide
+// enough for Z [N x (TP + dPHI)] after it (bit 1), when they fit
+struct PhiPlan {
+  size_t lds;
+  int stage_eta;
+};
+inline PhiPlan phi_plan(int N, int TP, int dPHI) {
+  const size_t lds = (size_t)(4 * N * (N + 1)) * sizeof(double);
+  const size_t staged = lds + (size_t)N * (TP + 1) * sizeof(double);
+  const size_t staged_z = lds + (size_t)N * std::max(TP + 1, TP + dPHI) * sizeof(double);
+  return staged_z <= kLdsCu ? PhiPlan{staged_z, 3} : (staged <= kLdsCu ? PhiPlan{staged, 1} : PhiPlan{lds, 0});
+}
+hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs);
+
 __global__ void k_sv_mix(Dims d, const int* __restrict__ Tslot, ChainState cs, RngArgs ra);
 __global__ void k_phi_gen(Dims d, const int* __restrict__ Tslot, int dPHI, ChainState cs, RngArgs ra);
-__global__ void k_phi(Dims d, const int* __restrict__ Tslot, int dPHI, const double* __restrict__ sPHIall,
-                      ChainState cs, int stage_eta);
 __global__ void k_store(Dims d, ChainState cs, Store st);
 __global__ void k_pai_moments(const double* __restrict__ sPAI, int cap, int m0, int m1, int per, int B,
                               double* __restrict__ sum, double* __restrict__ sumsq);

@@ -140,7 +140,7 @@ SCHEDULES = ([dict(elb_waves=w, elb_async=a, elb_parts=1, elb_oct=0) for w in (4
 
 # =============================================================================================
 def cond_launch(N, p, Ns):
-    """(threads, a_lds, kb_cond) of the k_elb_cond launch (ccmm_chains::run_elb): W_k of kb_cond lags at
+    """(threads, a_lds, kb_cond) of the k_elb_cond launch (ccmm_elb.h elb_cond_plan): W_k of kb_cond lags at
     once within 96 KB of LDS, A staged beside them when the whole stays within 64 KB, four waves
     instead of two when N > 64."""
     lds0 = ((p + 1) * Ns * N + (1 + 2 * p * Ns) * Ns + 2 * Ns * Ns + N * p * Ns) * 8
@@ -152,7 +152,7 @@ def cond_launch(N, p, Ns):
 
 
 def gibbs_waves(T, Ns, want):
-    """Passes in flight of the wave kernels for option elb_waves = want (ccmm_chains::run_elb): the
+    """Passes in flight of the wave kernels for option elb_waves = want (ccmm_elb.h elb_gibbs_waves): the
     LDS of W passes must fit 160 KB, else 8 -> 4 -> 1."""
     def lds(w):
         return 3 * T * Ns * 8 + T * 4 if w == 1 else (1 + 2 * w) * T * Ns * 8 + 2 * T * 4 + (2 * w + 1) * 4

@@ -1,0 +1,65 @@
+// Prints the launch plans and LDS layouts that the library's headers compute, one line per query read
+// from standard input (tests/test_launch_plans.py).  Host code only: no HIP runtime call.
+//
+//   cond N p Ns                -> threads a_lds kb lds
+//   waves elbTmax Ns want      -> W
+//   prep N p elbTmax B         -> lds phi_lds rows wg
+//   wf elbTmax Ns W            -> bytes, then name:offset of every region in layout order
+//   mp elbTmax Ns WPC          -> the same for k_elb_gibbs_mp
+//   oct elbTmax Ns             -> the same for k_elb_gibbs_oct
+//   draw1 W elbTmax nmax res   -> the same for k_ps_draw1
+//   misc N K KP TP dPHI        -> n_bucket, the A-step and PHI plans, whether the other kernels' LDS fits a CU
+#include <cstdio>
+#include <cstring>
+
+#include "ccmm_elb.h"
+#include "ccmm_fcst.h"
+#include "ccmm_lag.h"
+#include "ccmm_sweep.h"
+
+using namespace ccmm;
+
+static void wave(const ElbWaveLds& l) {
+  std::printf("%zu Sl:%zu Ul:%zu Zl:%zu Tm:%zu reach:%zu prog:%zu spare:%zu\n", l.end, l.Sl, l.Ul, l.Zl, l.Tm,
+              l.reach, l.prog, l.spare);
+}
+
+int main() {
+  char cmd[16];
+  int a, b, c, d, e;
+  while (std::scanf("%15s", cmd) == 1) {
+    if (!std::strcmp(cmd, "cond") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
+      const ElbCondPlan pl = elb_cond_plan(a, b, c);
+      std::printf("%d %d %d %zu\n", pl.threads, pl.a_lds, pl.kb, pl.lds);
+    } else if (!std::strcmp(cmd, "waves") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
+      std::printf("%d\n", elb_gibbs_waves(a, b, c));
+    } else if (!std::strcmp(cmd, "prep") && std::scanf("%d %d %d %d", &a, &b, &c, &d) == 4) {
+      const ElbPrepPlan pl = elb_prep_plan(a, b, c, d);
+      std::printf("%zu %d %d %d\n", pl.lds, pl.phi_lds, pl.rows, pl.wg);
+    } else if (!std::strcmp(cmd, "wf") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
+      wave(elb_wf_lds(a, b, c));
+    } else if (!std::strcmp(cmd, "mp") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
+      wave(elb_mp_lds(a, b, c));
+    } else if (!std::strcmp(cmd, "oct") && std::scanf("%d %d", &a, &b) == 2) {
+      const ElbOctLds l = elb_oct_lds(a, b);
+      std::printf("%zu Sl:%zu Tm:%zu reach:%zu\n", l.end, l.Sl, l.Tm, l.reach);
+    } else if (!std::strcmp(cmd, "draw1") && std::scanf("%d %d %d %d", &a, &b, &c, &d) == 4) {
+      const PsDraw1Lds l = ps_draw1_lds(a, b, c, d);
+      std::printf("%zu prow:%zu pb:%zu sL:%zu ybl:%zu zl:%zu Ll:%zu scens:%zu info:%zu cellL:%zu\n", l.end, l.prow,
+                  l.pb, l.sL, l.ybl, l.zl, l.Ll, l.scens, l.info, l.cellL);
+    } else if (!std::strcmp(cmd, "misc") && std::scanf("%d %d %d %d %d", &a, &b, &c, &d, &e) == 5) {
+      const AstepPlan as = astep_plan(a, d);
+      const PhiPlan ph = phi_plan(a, d, e);
+      // (the last three: whether the generic CTA kernels, the score kernel and the lag solve fit one CU's LDS)
+      std::printf("%d %zu %d %zu %d %d %d %d\n", n_bucket(a), as.lds, as.es_off, ph.lds, ph.stage_eta,
+                  (int)(std::max(gram_chol_lds_bytes(c / 16), cta_solve2_lds_bytes(a, c, d)) <= kLdsCu &&
+                        resid_multi_lds_bytes(a, b) <= kLdsCu),
+                  (int)(fcst_scores_lds_doubles(a) * sizeof(double) <= kLdsCu),
+                  (int)(sl_lds_bytes(1, d + 8, a + 1, d, n_bucket(a)) <= kLdsCu));
+    } else {
+      std::fprintf(stderr, "bad query: %s\n", cmd);
+      return 2;
+    }
+  }
+  return 0;
+}

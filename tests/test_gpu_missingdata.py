@@ -148,6 +148,7 @@ def _spill_bs(bh):
 
 
 PANELS = {"toy_w16": (lambda bh, o, f: _toy_bs(bh, (80, 120)), 16, None, 4),
+          "toy_w32": (lambda bh, o, f: _toy_bs(bh, (100, 120), p=15), 32, 1, 2),
           "real_w48": (_real_bs, 48, 1, 2),
           "ns5_w80": (lambda bh, o, f: _ns5_bs(bh), 80, None, 2),
           "spill_w64": (lambda bh, o, f: _spill_bs(bh), 64, 0, 2)}
@@ -205,6 +206,28 @@ def test_missing_unfused_pair_matches_fused(pkg, ctx, oracle, bh):
     for m, P in outs[1:]:
         np.testing.assert_array_equal(m, outs[0][0])
         np.testing.assert_array_equal(P, outs[0][1])
+
+
+@pytest.mark.parametrize("panel", ["toy_w32", "real_w48", "spill_w64"])
+def test_missing_unfused_pair_matches_fused_wider_bands(pkg, ctx, oracle, bh, fred, panel):
+    """The same at the wider band buckets: k_ps_chol_w<W> + k_ps_apply<W, forced> against k_ps_draw1<W>, one
+    Philox sweep of two chains that differ in their Philox streams."""
+    make, W, _, _ = PANELS[panel]
+    bs = make(bh, oracle, fred)
+    assert _band(bs)[0] == W
+    st = oracle.init_state(bs.lin)
+    B, outs = 2, []
+    for fused in (True, False):
+        ch = _chains(pkg, ctx, bs, pkg.MODEL_BLOCKHYBRID, B, crn=False, cap=1, seed=99)
+        ch.set_elb_treatment(missing=True, fused=fused)
+        ch.set_state(*[np.repeat(st[k][..., None], B, -1) for k in STATE])
+        ch.sweep(1, store=True)
+        assert np.all(ch.get_status() == 0)
+        outs.append((ch.get_missingrate(), ch.get_state()["PAI"]))
+        ch.close()
+    assert not np.array_equal(outs[0][0][..., 0], outs[0][0][..., 1])  # the chains differ
+    np.testing.assert_array_equal(outs[1][0], outs[0][0])
+    np.testing.assert_array_equal(outs[1][1], outs[0][1])
 
 
 # ---------------------------------------------------------------- the alternate draw

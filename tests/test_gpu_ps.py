@@ -19,10 +19,10 @@ def bh():
     return ccmm_oracle_bh
 
 
-def _toy_bs(bh, window, seed=3, valley=False):
+def _toy_bs(bh, window, seed=3, valley=False, p=2):
     """Toy block-hybrid panel; valley=True lets the shadow rates glide down to the ELB
     around the window (so the conditional means of the censored cells sit near it)."""
-    N, p, Tobs, ndxS, ndxO = 5, 2, 150, (2, 3), (4,)
+    N, Tobs, ndxS, ndxO = 5, 150, (2, 3), (4,)
     data = synth_bh_data(N, p, Tobs, elb_window=window, ndxS=ndxS, seed=seed)
     if valley:
         a, b = window
@@ -127,6 +127,18 @@ def test_ps_toy_long_window_fallback(pkg, ctx, oracle, bh):
     Gibbs fallback (:462-463) serves most sweeps."""
     bs = _toy_bs(bh, (80, 120))
     got, S, ps, want = _run(pkg, ctx, oracle, bh, bs, B=3, nsweeps=2, NP=64, seed=5)
+    _check(oracle, bs, got, S, ps, want, 1e-9)
+
+
+def test_ps_toy_band_width_32(pkg, ctx, oracle, bh):
+    """p = 15 with the toy's two rates over twenty months: up to Ns (p + 1) = 32 censored cells within p months
+    of each other, the 32-wide kernels (k_ps_chol_w<32>, k_ps_prop<32>, k_ps_apply<32>), which neither the toy
+    windows (band bucket 16) nor the real one (48) reach."""
+    bs = _toy_bs(bh, (100, 120), p=15)
+    months = np.repeat(np.arange(bs.elbT), bs.sNaN.sum(axis=0))   # month of every censored cell, in cell order
+    width = int(np.max(np.arange(months.size) - np.searchsorted(months, months - bs.lin.p) + 1))
+    assert 16 < width <= 32, width
+    got, S, ps, want = _run(pkg, ctx, oracle, bh, bs, B=2, nsweeps=2, NP=64, seed=17)
     _check(oracle, bs, got, S, ps, want, 1e-9)
 
 

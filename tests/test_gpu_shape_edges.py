@@ -6,8 +6,9 @@ Tolerances are the project's: 1e-9 in units of max(|x|, posterior sd) for well-c
 systems (tests/test_gpu_parity.py), bit-exactness for the mirror contract (tests/test_gpu_mirror.py),
 the KSC indicators and for schedules that keep the operation order.
 
-Which test launches which variant (from the dispatch in ccmm_abi.hip run_cta / run_resid /
-run_astep, ccmm_lag.hip lag_launch_*, ccmm_svpart.hip sv_launch_part; KP = round_up(K, 64),
+Which test launches which variant (from the dispatch in ccmm_kernels.hip launch_resid / launch_astep,
+ccmm_gram_chol.hip launch_gram_chol, ccmm_cta_solve.hip launch_cta_solve2, ccmm_lag.hip lag_launch_*,
+ccmm_svpart.hip sv_launch_part; KP = round_up(K, 64),
 TP = round_up(T, 32)):
 
   test_cta_k_edges        k_gram_chol<KP/16>: <4> K = 9, 64; <8> K = 65, 127, 128; <12> K = 129, 192;
@@ -95,7 +96,7 @@ def test_cta_n_buckets(ctx, T, N, K, sys):
 @pytest.mark.parametrize("T,N,K", sc.CTA_RESID_MULTI)
 def test_cta_resid_multi(ctx, T, N, K):
     """B = 17 takes k_resid_multi, B = 2 k_resid: the same fma order per equation
-    (ccmm_abi.hip run_resid), so every chain repeats the B = 2 draw bit for bit."""
+    (ccmm_kernels.hip launch_resid), so every chain repeats the B = 2 draw bit for bit."""
     d = sc.cta_inputs(T, N, K)
     got2 = _cta_run(ctx, d, 2)
     got17 = _cta_run(ctx, d, 17)

@@ -1,0 +1,139 @@
+"""The library's own launch arithmetic, on the CPU: tests/launch_plans_main.cpp includes the kernel units'
+headers (ccmm_elb.h, ccmm_sweep.h, ccmm_fcst.h, ccmm_lag.h), calls no HIP runtime function and prints the plans
+and LDS layouts the host launchers use.  Checked against the restatements of tests/elb_cases.py on every ELB
+edge case, so that the edge asserts there (n65_lagbatch -> kb 10, long_w4 -> 4, long_w1 -> 1) are statements
+about the library, and against the layout comments of the kernels region by region."""
+import subprocess
+
+import pytest
+
+import elb_cases as EC
+from conftest import ROOT
+
+CSRC = ROOT / "ccmmshadowratevar-code_amd" / "csrc"
+LDS_CU = 160 * 1024
+WANTS = (1, 4, 8)
+
+
+@pytest.fixture(scope="module")
+def plans(tmp_path_factory):
+    """query(lines) -> one list of output tokens per line, from one run of the compiled program."""
+    exe = tmp_path_factory.mktemp("launch_plans") / "launch_plans"
+    subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-O1", "-I", str(CSRC),
+                    "-I", str(ROOT / "include"), str(ROOT / "tests" / "launch_plans_main.cpp"), "-o", str(exe)],
+                   check=True)
+
+    def query(lines):
+        out = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True)
+        rows = [r.split() for r in out.stdout.splitlines()]
+        assert len(rows) == len(lines)
+        return rows
+    return query
+
+
+def _layout(row):
+    """(total bytes, [(region, offset)] in layout order) of a layout line."""
+    return int(row[0]), [(t.split(":")[0], int(t.split(":")[1])) for t in row[1:]]
+
+
+def _check_layout(row, sizes, doubles):
+    """The regions start at 0, follow each other without gap or overlap in the order and with the sizes the
+    kernel's layout comment gives, end at the size the launcher asks for, and the double regions are 8-byte
+    aligned."""
+    total, regions = _layout(row)
+    assert [r for r, _ in regions] == [r for r, _ in sizes]
+    off = 0
+    for (name, got), (_, size) in zip(regions, sizes):
+        assert got == off, (name, got, off)
+        assert name not in doubles or got % 8 == 0, name
+        off += size
+    assert total == off
+
+
+def test_cond_plan_and_gibbs_waves_match_the_restatement(plans):
+    names = list(EC.CASES)
+    cases = [EC.CASES[n] for n in names]
+    cond = plans([f"cond {c.Ny} {c.p} {c.Ns}" for c in cases])
+    for c, row in zip(cases, cond):
+        assert tuple(map(int, row[:3])) == EC.cond_launch(c.Ny, c.p, c.Ns), c.name
+        assert int(row[3]) <= 96 * 1024 + c.Ny * c.Ny * 8 and int(row[3]) <= LDS_CU, c.name
+    waves = plans([f"waves {c.T} {c.Ns} {w}" for c in cases for w in WANTS])
+    got = {(c.name, w): int(r[0]) for (c, w), r in zip(((c, w) for c in cases for w in WANTS), waves)}
+    for c in cases:
+        for w in WANTS:
+            assert got[c.name, w] == EC.gibbs_waves(c.T, c.Ns, w), (c.name, w)
+    # the edges the cases were built for
+    assert tuple(map(int, cond[names.index("n65_lagbatch")][:3])) == (256, 0, 10)
+    assert [got["long_w4", w] for w in WANTS] == [1, 4, 4]
+    assert [got["long_w1", w] for w in WANTS] == [1, 1, 1]
+
+
+def test_wave_kernel_lds_layouts(plans):
+    cases = list(EC.CASES.values())
+    waves = plans([f"waves {c.T} {c.Ns} {w}" for c in cases for w in WANTS])
+    q, want = [], []
+    for (c, w), r in zip(((c, w) for c in cases for w in WANTS), waves):
+        W, pg, it = int(r[0]), c.T * c.Ns * 8, c.T * 4
+        if W > 1:  # k_elb_gibbs_wf: Sl | Ul[W] | Zl[W] | Tm | reach | prog[2][W] | one spare int
+            q.append(f"wf {c.T} {c.Ns} {W}")
+            want.append([("Sl", pg), ("Ul", W * pg), ("Zl", W * pg), ("Tm", it), ("reach", it), ("prog", 2 * W * 4),
+                         ("spare", 4)])
+        if W == 8:  # k_elb_gibbs_mp<NS, WPC, 8 / WPC>: the same with WPC waves and prog[WPC + 1]
+            for wpc in (4, 2):
+                q.append(f"mp {c.T} {c.Ns} {wpc}")
+                want.append([("Sl", pg), ("Ul", wpc * pg), ("Zl", wpc * pg), ("Tm", it), ("reach", it),
+                             ("prog", (wpc + 1) * 4), ("spare", 4)])
+    assert any(x.startswith("wf") and x.endswith(" 4") for x in q) and any(x.startswith("mp") for x in q)
+    for line, row, sizes in zip(q, plans(q), want):
+        _check_layout(row, sizes, {"Sl", "Ul", "Zl"})
+        assert int(row[0]) <= LDS_CU, line  # every W elb_gibbs_waves returns fits one CU's LDS
+
+
+def test_octet_and_draw1_lds_layouts(plans):
+    cases = list(EC.CASES.values())
+    q = [f"oct {c.T} {c.Ns}" for c in cases]
+    for c, row in zip(cases, plans(q)):
+        _check_layout(row, [("Sl", c.T * c.Ns * 8), ("Tm", c.T * 4), ("reach", c.T * 4)], {"Sl"})
+    # k_ps_draw1<W>: k_ps_chol_w's doubles, L^-1 b, the normals, the resident band rows, then the int lists;
+    # nmax = the case's censored cells (odd counts included: the ints follow the doubles)
+    q, want = [], []
+    for c in cases:
+        nmax = int(EC.mask_of(c).sum())
+        for W in (16, 32, 48, 64):
+            for res in (0, 1):
+                q.append(f"draw1 {W} {c.T} {nmax} {res}")
+                want.append([("prow", 64 * W * 8), ("pb", 64 * 8), ("sL", W * 8), ("ybl", nmax * 8), ("zl", nmax * 8),
+                             ("Ll", res * nmax * W * 8), ("scens", c.T * 4), ("info", nmax * 4), ("cellL", nmax * 4)])
+    for row, sizes in zip(plans(q), want):
+        _check_layout(row, sizes, {"prow", "pb", "sL", "ybl", "zl", "Ll"})
+
+
+def test_prep_and_sweep_plans(plans):
+    # k_elb_prep: X0 | Phi | Yb - yhat | Yb while they fit; the row split below 128 chains
+    def prep(N, p, T, B):
+        lds, phi = (2 + N * p + N * (N * p + 1)) * 8, 1
+        if lds > LDS_CU:
+            lds, phi = (2 + N * p) * 8, 0
+        if phi and lds + 2 * T * N * 8 <= LDS_CU:
+            lds, phi = lds + 2 * T * N * 8, 3
+        rows, wg = 0, 1
+        if phi & 2 and B < 128:
+            per = max(1, 256 // B)
+            rows = max(16, -(-T // per))
+            wg = -(-T // rows)
+        return [lds, phi, rows, wg]
+    shapes = [(c.Ny, c.p, c.T, c.B) for c in EC.CASES.values()] + [(20, 12, 165, 256), (20, 12, 165, 1), (120, 12, 165, 4)]
+    for s, row in zip(shapes, plans(["prep %d %d %d %d" % s for s in shapes])):
+        assert list(map(int, row)) == prep(*s), s
+    assert prep(20, 12, 165, 256)[1] == 3 and prep(120, 12, 165, 4)[1] == 0 and prep(20, 12, 165, 1)[3] > 1
+    # the per-chain kernels' bucket and the staging decisions of the A-step and PHI (N = 20, T = 750: E staged,
+    # 138 KB in all; N = 32 at TP = 768: neither E nor eta fits beside the rest)
+    rows = plans(["misc 20 241 256 768 22", "misc 32 385 448 768 34", "misc 8 17 64 96 10", "misc 9 19 64 96 11"])
+    r20, r32, r8, r9 = ([int(x) for x in r] for r in rows)
+    assert (r20[0], r32[0], r8[0], r9[0]) == (20, 32, 8, 20)
+    tot = 19 * 20 * 21 // 6 + 20 * 19 // 2 + 8
+    assert r20[1:3] == [(tot + 400 + 20 * 768) * 8, tot + 400] and 138_000 < r20[1] <= LDS_CU
+    assert r20[3:5] == [(4 * 20 * 21 + 20 * 790) * 8, 3]
+    assert r32[2] == -1 and r32[4] == 0 and r32[3] == 4 * 32 * 33 * 8
+    assert all(r[1] <= LDS_CU and r[3] <= LDS_CU and r[5:7] == [1, 1] for r in (r20, r32, r8, r9))
+    assert (r8[7], r32[7]) == (1, 0)  # the lag solve's resident design: N = 8 at TP = 96 fits, N = 32 at 768 does not
