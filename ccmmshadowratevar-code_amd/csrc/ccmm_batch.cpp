@@ -8,10 +8,7 @@
 #include <vector>
 
 #include "../../include/ccmm.h"
-
-namespace ccmm {
-void set_last_error(const std::string& msg);  // ccmm_abi.hip
-}
+#include "ccmm_err.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // Large-system CTA (ccmm_big.hip, its own translation unit): host launchers used by
-// ccmm_abi.hip when K > 512 or N > 32 (the S120 configuration N = 120, K = 1441).
+// ccmm_chains_sweep.hip when K > 512 or N > 32 (the S120 configuration N = 120, K = 1441).
 #pragma once
 #include "ccmm_internal.h"
 

@@ -1,5 +1,5 @@
 // Large-N Gibbs blocks (ccmm_bign.hip, its own translation unit): A-step, PHI and SV for
-// 32 < N <= 128, used by ccmm_abi.hip in place of the per-chain small-matrix kernels.
+// 32 < N <= 128, used by ccmm_chains_sweep.hip in place of the per-chain small-matrix kernels.
 #pragma once
 #include "ccmm_internal.h"
 

@@ -1,7 +1,7 @@
 // Device views, record layouts, LDS sizes, launch decisions and host launchers of the ELB shadow-rate step and
 // its acceptance-sampling branch.  The kernels are defined in their own translation units, ccmm_elb.hip and
 // ccmm_ps.hip, each with the launchers that pick (and so instantiate) its template arguments; this header is
-// what the host side (ccmm_abi.hip) and the predictive-density kernels see.  The size and decision functions
+// what the host side (ccmm_chains_elb.hip) and the predictive-density kernels see.  The size and decision functions
 // make no HIP call (tests/launch_plans_main.cpp prints them on the host).
 #pragma once
 #include <algorithm>

@@ -1,5 +1,5 @@
 // Lag-structured CTA path (kernels in ccmm_lag.hip, its own translation unit):
-// device views, LDS budgets and host launchers used by ccmm_abi.hip.
+// device views, LDS budgets and host launchers used by ccmm_chains.hip and ccmm_chains_sweep.hip.
 #pragma once
 #include <algorithm>
 

@@ -1,5 +1,5 @@
 // Partitioned SV sampler (kernels in ccmm_svpart.hip, its own translation unit):
-// buffer sizes and the host launcher used by ccmm_abi.hip.
+// buffer sizes and the host launcher used by ccmm_chains_sweep.hip.
 #pragma once
 #include "ccmm_internal.h"
 

@@ -2,7 +2,7 @@
 X = [1, lags 1..p of shadowYdata, lags 1..p of the actual rates floored at the ELB]
 (mcmcVARhybridGibbs.m:69-84, rebuilt every sweep at :521-525), so the large path's Gram and solve
 can read the column-major slab ("lag twin", ccmm_big.h ColX) instead of the K x T design.  CPU
-restatement of the twin's column map (ChainSet::init_colx / try_upload_Dc in csrc/ccmm_abi.hip)
+restatement of the twin's column map (ccmm_chains::init_colx / try_upload_Dc in csrc/ccmm_chains.hip)
 checked against the reference's own construction, before and after shadow-rate draws replace the
 censored months -- every row of the sample, the ones after the shadow window included."""
 import numpy as np
