@@ -360,6 +360,8 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
     for (int i = 0; i < N; ++i) nwx += ndxYields[i] ? 0 : 1;
     require(nwx > 0 && nwx < N, "need at least one macro series and one yield");
     HIPCHECK(hipSetDevice(ctx->device));
+    // (the LDS form's size even where the register path will run: it refuses no register-path shape, whose
+    // largest, N = 21, p = 12 at hc = 1, is 253 * 21 + 2 * 441 + 2 * 252 + 63 = 6762 doubles, 53 KB)
     require(fcst_paths_lds_doubles(N, K, p, fcst_chunk(N, K, p, H)) * sizeof(double) <= kLdsCu,
             "forecast state does not fit LDS");
     auto up = [&](DBuf<double>& d, const double* h, size_t n) {

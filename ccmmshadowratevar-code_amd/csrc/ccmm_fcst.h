@@ -85,6 +85,13 @@ inline int fcst_chunk(int N, int Kx, int p, int H, bool reg = false) {
   return hc;
 }
 
+// the k_fcst<RN> instance launch_fcst takes: kFcstRegN - 1 (even N below kFcstRegN), kFcstRegN (the other
+// register-path shapes) or 0 (PAI in LDS).  reg_opt: option fcst_reg
+inline int fcst_variant(int N, int p, int bh, bool reg_opt) {
+  const bool reg = fcst_reg_path(N, p, bh) && reg_opt;
+  return !reg ? 0 : (N % 2 == 0 && N < kFcstRegN ? kFcstRegN - 1 : kFcstRegN);
+}
+
 // k_fcst<RN> then k_fcst_scores of one kept draw per chain; sets a.hc and a.sv1.  reg_opt: option fcst_reg.
 // Throws std::runtime_error when the paths' state does not fit one CU's LDS
 hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt);

@@ -72,35 +72,26 @@ __device__ double bvnu(double dh, double dk, double r, const GLNodes& gl) {
   return fmax(0.0, fmin(1.0, bvn));
 }
 
-// Trivariate normal P(X <= x), X ~ N(0, L L') with L lower 3x3 (ld kFcstMaxN at M):
-// P = int_{-inf}^{x1/L11} phi(z) BVN(h(z), k(z); rho) dz with the conditional
-// bivariate of (X2, X3) | z (Genz BVN inside).  The integrand steps where h or k
-// changes sign, so the outer interval is split there and each segment integrated
-// on panels graded geometrically towards both ends (20-point Gauss-Legendre):
-// panel j of a side spans [w0 (2^j - 1), min(w0 (2^(j+1) - 1), half)] from that end.
-// MATLAB's mvncdf (trivariate rule, absolute tolerance 1e-8) is the reference.
-// Called by all 64 lanes of a wave with identical arguments: the (segment, side, panel,
-// node) evaluations are spread over the lanes and summed with one wave reduction.
-__device__ double tvn_cdf(const double* x, const double* M, const GLNodes& gl, int lane) {
-  const double l11 = M[0], l21 = M[1], l31 = M[2];
-  const double l22 = M[1 + kFcstMaxN], l32 = M[2 + kFcstMaxN], l33 = M[2 + 2 * kFcstMaxN];
-  const double s3 = sqrt(l32 * l32 + l33 * l33), rho = l32 / s3;
-  const double b = x[0] / l11;
-  const double lo = -10.0, w0 = 1e-4;
-  if (b <= lo) return 0.0;
-  double brk[4];
-  int nb = 0;
-  brk[nb++] = lo;
-  double cand[2] = {l21 != 0.0 ? x[1] / l21 : lo, l31 != 0.0 ? x[2] / l31 : lo};
-  if (cand[0] > cand[1]) { const double t = cand[0]; cand[0] = cand[1]; cand[1] = t; }
-  for (int i = 0; i < 2; ++i)
-    if (cand[i] > brk[nb - 1] + 1e-12 && cand[i] < b - 1e-12) brk[nb++] = cand[i];
-  brk[nb++] = b;
+// A composite 20-point Gauss-Legendre rule on [brk[0], brk[nb-1]] split at the interior break points, every
+// segment on panels graded geometrically towards both of its ends: panel j of a side spans
+// [w0 (2^j - 1), min(w0 (2^(j+1) - 1), half)] from that end (half = half the segment).  Called by all 64 lanes of
+// a wave with identical arguments: the (segment, side, panel, node) evaluations are spread over the lanes;
+// returns this lane's part of sum f(z, weight) * (panel half-width), the caller adds the lanes up.
+struct GradedRule {
+  double brk[6];
+  int nb;
+  double w0;
+};
+
+template <class F>
+__device__ double graded_gl20(const GradedRule& g, const GLNodes& gl, int lane, F f) {
+  const double w0 = g.w0;
+  const int nb = g.nb;
   // panels per side of each segment
-  int npan[3];
+  int npan[5];
   int total = 0;
   for (int sgm = 0; sgm + 1 < nb; ++sgm) {
-    const double half = 0.5 * (brk[sgm + 1] - brk[sgm]);
+    const double half = 0.5 * (g.brk[sgm + 1] - g.brk[sgm]);
     int n = 0;
     double pos = 0.0, w = fmin(w0, half);
     while (pos < half) {
@@ -118,7 +109,7 @@ __device__ double tvn_cdf(const double* x, const double* M, const GLNodes& gl, i
     const int side = rem / (npan[sgm] * 20);
     rem -= side * npan[sgm] * 20;
     const int j = rem / 20, node = rem - j * 20;
-    const double a0 = brk[sgm], a1 = brk[sgm + 1];
+    const double a0 = g.brk[sgm], a1 = g.brk[sgm + 1];
     const double half = 0.5 * (a1 - a0);
     const double wj = fmin(w0, half) * exp2((double)j);
     const double u0 = (j == 0) ? 0.0 : fmin(w0, half) * (exp2((double)j) - 1.0);
@@ -128,9 +119,72 @@ __device__ double tvn_cdf(const double* x, const double* M, const GLNodes& gl, i
     const double sg = (node & 1) ? 1.0 : -1.0;
     const double u = c + sg * r * gl.x[2][i];
     const double z = side == 0 ? a0 + u : a1 - u;
-    const double h = (x[1] - l21 * z) / l22, k = (x[2] - l31 * z) / s3;
-    acc += gl.w[2][i] * exp(-0.5 * z * z) * bvnu(-h, -k, rho, gl) * r;
+    acc += f(z, gl.w[2][i]) * r;
   }
+  return acc;
+}
+
+// P(X <= h, Y <= k) for standard normals with correlation r, to relative accuracy: the conditional integral
+// int_lo^h phi(z) Phi((k - r z) / s) dz, s = sqrt(1 - r^2).  For the deep tails, where BVNU's absolute 1e-16
+// (the accuracy Genz states, and MATLAB's mvncdf has) leaves the logarithm of the probability no digits or
+// turns it into log(0).  The integrand is log-concave with its mode in [min(r k, 0), max(r k, 0)] (clipped
+// at h) and curvature at least 1, so below lo = min(h, r k, 0) - 9 lies 1e-19 of it at most; it is split at
+// r k (its peak, of width s, where Phi is small), at k / r (where the inner argument changes sign; panels down
+// to a quarter of the transition's width s / |r|) and at 0.  Called by all 64 lanes with identical arguments.
+__device__ double bvn_cond(double h, double k, double r, const GLNodes& gl, int lane) {
+  if (r == 0.0) return ncdf(h) * ncdf(k);
+  const double s = sqrt((1.0 - r) * (1.0 + r));
+  if (!(s > 0.0)) return r > 0.0 ? ncdf(fmin(h, k)) : fmax(0.0, ncdf(h) - ncdf(-k));
+  const double hi = fmin(h, 40.0);
+  double cand[3] = {r * k, k / r, 0.0};
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j + 1 < 3 - i; ++j)
+      if (cand[j] > cand[j + 1]) { const double t = cand[j]; cand[j] = cand[j + 1]; cand[j + 1] = t; }
+  GradedRule g;
+  g.w0 = fmax(fmin(1e-4, 0.25 * s / fabs(r)), 1e-12);
+  g.nb = 0;
+  g.brk[g.nb++] = fmin(fmin(hi, r * k), 0.0) - 9.0;
+  for (int i = 0; i < 3; ++i)
+    if (cand[i] > g.brk[g.nb - 1] + 1e-12 && cand[i] < hi - 1e-12) g.brk[g.nb++] = cand[i];
+  g.brk[g.nb++] = hi;
+  const double acc = graded_gl20(g, gl, lane, [&](double z, double w) {
+    return w * exp(-0.5 * z * z) * ncdf((k - r * z) / s);
+  });
+  return fmax(0.0, fmin(1.0, wave_sum(acc) * 0.39894228040143267794));
+}
+
+// below this BVNU's absolute accuracy no longer gives the log score its 1e-9: bvn_cond takes over
+constexpr double kBvnRelFloor = 1e-7;
+
+// Trivariate normal P(X <= x), X ~ N(0, L L') with L lower 3x3 (ld kFcstMaxN at M):
+// P = int_{lo}^{x1/L11} phi(z) BVN(h(z), k(z); rho) dz with the conditional
+// bivariate of (X2, X3) | z (Genz BVN inside).  The integrand steps where h or k
+// changes sign, so the outer interval is split there and each segment integrated
+// on graded panels (graded_gl20, w0 = 1e-4).  The lower limit lo = min(-10, b - 5), b = x1 / L11, leaves
+// out at most exp(-37.5) = 5e-17 of the Gaussian weight at b (Phi(-10) = 8e-24 for b >= -5), so that the
+// logarithm keeps its digits for b far in the tail as well; b <= -38.6: Phi(b) is 0 in fp64.
+// MATLAB's mvncdf (trivariate rule, absolute tolerance 1e-8) is the reference.
+// Called by all 64 lanes of a wave with identical arguments.
+__device__ double tvn_cdf(const double* x, const double* M, const GLNodes& gl, int lane) {
+  const double l11 = M[0], l21 = M[1], l31 = M[2];
+  const double l22 = M[1 + kFcstMaxN], l32 = M[2 + kFcstMaxN], l33 = M[2 + 2 * kFcstMaxN];
+  const double s3 = sqrt(l32 * l32 + l33 * l33), rho = l32 / s3;
+  const double b = x[0] / l11;
+  if (b <= -38.6) return 0.0;
+  const double lo = fmin(-10.0, b - 5.0);
+  GradedRule g;
+  g.w0 = 1e-4;
+  g.nb = 0;
+  g.brk[g.nb++] = lo;
+  double cand[2] = {l21 != 0.0 ? x[1] / l21 : lo, l31 != 0.0 ? x[2] / l31 : lo};
+  if (cand[0] > cand[1]) { const double t = cand[0]; cand[0] = cand[1]; cand[1] = t; }
+  for (int i = 0; i < 2; ++i)
+    if (cand[i] > g.brk[g.nb - 1] + 1e-12 && cand[i] < b - 1e-12) g.brk[g.nb++] = cand[i];
+  g.brk[g.nb++] = b;
+  const double acc = graded_gl20(g, gl, lane, [&](double z, double w) {
+    const double h = (x[1] - l21 * z) / l22, k = (x[2] - l31 * z) / s3;
+    return w * exp(-0.5 * z * z) * bvnu(-h, -k, rho, gl);
+  });
   return fmax(0.0, fmin(1.0, wave_sum(acc) * 0.39894228040143267794));  // Genz TVNU: MAX(0, MIN(1, TVN))
 }
 
@@ -272,7 +326,9 @@ __device__ double score_censored(const double* invA, const double* sv, const dou
     const double s2 = sqrt(l21 * l21 + l22 * l22);
     const double rho = l21 / s2;
     const double h = (yat[0] - y21[0]) / l11, k = (yat[1] - y21[1]) / s2;
-    llf2 = log(bvnu(-h, -k, rho, gl));
+    double P = bvnu(-h, -k, rho, gl);
+    if (P < kBvnRelFloor) P = bvn_cond(h, k, rho, gl, lane);
+    llf2 = log(P);
   } else if (nat == 3) {
     const double xv[3] = {yat[0] - y21[0], yat[1] - y21[1], yat[2] - y21[2]};
     llf2 = log(tvn_cdf(xv, M + noff + noff * kFcstMaxN, gl, lane));
@@ -712,10 +768,10 @@ hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt) {
   const size_t ls = fcst_scores_lds_doubles(a.N) * sizeof(double);
   if (lp > kLdsCu) throw std::runtime_error("forecast state does not fit LDS");
   const dim3 g(a.bh ? a.Nd : a.Nd + 1, a.B);
-  const bool even = reg && a.N % 2 == 0 && a.N < kFcstRegN;
-  const hipError_t e = even  ? launch_k(k_fcst<kFcstRegN - 1>, g, dim3(64), lp, true, st, a)
-                       : reg ? launch_k(k_fcst<kFcstRegN>, g, dim3(64), lp, true, st, a)
-                             : launch_k(k_fcst<0>, g, dim3(64), lp, true, st, a);
+  const int rn = fcst_variant(a.N, a.p, a.bh, reg_opt);
+  const hipError_t e = rn == kFcstRegN - 1 ? launch_k(k_fcst<kFcstRegN - 1>, g, dim3(64), lp, true, st, a)
+                       : rn == kFcstRegN   ? launch_k(k_fcst<kFcstRegN>, g, dim3(64), lp, true, st, a)
+                                           : launch_k(k_fcst<0>, g, dim3(64), lp, true, st, a);
   if (e != hipSuccess) return e;
   return launch_k(k_fcst_scores, dim3(a.Nd, a.B), dim3(64), ls, true, st, a);
 }

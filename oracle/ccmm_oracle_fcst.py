@@ -7,7 +7,12 @@ linear companion simulation (ltitr), the one-step predictive log scores
 (logscoreGaussian.m:15-20, logscoreGaussianCensored.m:13-88), the censored
 simulation (:354-372) and the Rao-Blackwellised mean path (:375-379).
 
-PARITY UNPINNED (MATLAB reference, no fixtures).  MATLAB built-ins restated:
+PARITY: no MATLAB fixtures; the cdf restatements below are pinned to 40-digit values on the structured grid
+of tests/mvncdf_grid.py (tests/test_oracle_fcst.py: normcdf and the two- and three-series quadratures at the
+project's 1e-9 / 1e-8 on the log score, apart from the 15 named points of mvncdf_grid.ORACLE_MISSES -- scipy's
+ndtr at a subnormal probability, and the adaptive rule stepping over an inner transition 1e-3 .. 1e-6 wide at
+|r| >= 1 - 1e-6; the lattice rule inside 1e-4 of the one-factor truth, measured 5.2e-6 at worst).  The
+simulations are pinned to longdouble restatements at 1e-11 (tests/test_refs.py).  MATLAB built-ins restated:
 ``normcdf`` exactly (erfc); ``mvncdf`` for 2 and 3 censored series by
 independent adaptive quadrature (scipy.integrate.quad) of the conditional
 univariate / bivariate integrals — MATLAB's own trivariate

@@ -9,6 +9,8 @@
 //   oct elbTmax Ns             -> the same for k_elb_gibbs_oct
 //   draw1 W elbTmax nmax res   -> the same for k_ps_draw1
 //   misc N K KP TP dPHI        -> n_bucket, the A-step and PHI plans, whether the other kernels' LDS fits a CU
+//   fcst N p H bh reg_opt      -> fcst_reg_path, fcst_chunk (register form, LDS form), the k_fcst<RN> instance and the
+//                                 chunk and LDS bytes launch_fcst takes with option fcst_reg = reg_opt (Kx = N p + 1)
 #include <cstdio>
 #include <cstring>
 
@@ -56,6 +58,13 @@ int main() {
                         resid_multi_lds_bytes(a, b) <= kLdsCu),
                   (int)(fcst_scores_lds_doubles(a) * sizeof(double) <= kLdsCu),
                   (int)(sl_lds_bytes(1, d + 8, a + 1, d, n_bucket(a)) <= kLdsCu));
+    } else if (!std::strcmp(cmd, "fcst") && std::scanf("%d %d %d %d %d", &a, &b, &c, &d, &e) == 5) {
+      const int Kx = a * b + 1;
+      const bool reg = fcst_reg_path(a, b, d) && e;
+      const int hc = fcst_chunk(a, Kx, b, c, reg);
+      std::printf("%d %d %d %d %d %zu\n", (int)fcst_reg_path(a, b, d), fcst_chunk(a, Kx, b, c, true),
+                  fcst_chunk(a, Kx, b, c, false), fcst_variant(a, b, d, e != 0), hc,
+                  fcst_paths_lds_doubles(a, Kx, b, hc, reg) * sizeof(double));
     } else {
       std::fprintf(stderr, "bad query: %s\n", cmd);
       return 2;

@@ -208,3 +208,160 @@ def elb_gibbs_ld(Y, STATE0, YHAT0, ndxS, sNaN, p, C, Psi, SVol, elb, burnin, u):
                     ub[a, t, n] = (elb - mu) / sd
                     PHIbar[a, t, n] = 0.5 * erfc(-np.sqrt(0.5) * ub[a, t, n])
     return Yl[ndx, :].astype(np.float64), flags, ub, PHIbar, sig
+
+
+# ------------------------------------------------------------------ predictive density (tests/fcst_cases.py)
+def _sv_nu_ld(invA, logSV0, sqrtPHI, svz, z):
+    """The shock side of one kept draw: logSV = logSV0 + cumsum(sqrtPHI randn, 2), sv = exp(logSV / 2),
+    nu = invA (sv .* z) (mcmcVAR.m:301-314; BlockHybrid.m:553-561, 612).  Returns sv, nu: N x H x Nd."""
+    N = invA.shape[0]
+    H, Nd = z.shape[1], z.shape[2]
+    shocks = (np.asarray(sqrtPHI).astype(LD) @ np.asarray(svz).astype(LD)).reshape(N, H, Nd, order="F")
+    logSV = np.asarray(logSV0).astype(LD)[:, None, None] + np.cumsum(shocks, axis=1)
+    sv = np.exp(logSV * LD(0.5))
+    w = sv * np.asarray(z).astype(LD)
+    nu = np.einsum("ij,jhn->ihn", np.asarray(invA).astype(LD), w)
+    return sv, nu
+
+
+def fcst_paths_ld(PAI, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, elb, svz, z, rec_floor=None):
+    """mcmcVAR.m:298-323, 354-379 for one kept draw in longdouble: the companion recursion on the explicit
+    state x = [1, y(t), ..., y(t-p+1)] (x <- [1; PAI' x + nu; x(2:K-N)], the rows fcstA has at :108-110, 317),
+    once without a floor (:320-323), once with the series of rec_floor (default ndxYields, :360-366; a
+    shadow-rate model passes ndxOTHERYIELDS) set to ELBbound inside the state when below it, and once with
+    zero shocks (:376-379).
+
+    Returns fY, fYc (N x H x Nd) and yhat (N x H) rounded to fp64, sv1 (N x Nd, longdouble: fcstSVdraws(:,1))
+    and the smallest |y - elb| over every floor comparison made."""
+    P = np.asarray(PAI).astype(LD)
+    K, N = P.shape
+    H, Nd = z.shape[1], z.shape[2]
+    fl = np.asarray(ndxYields if rec_floor is None else rec_floor, bool)
+    x0 = np.asarray(Xjumpoff).astype(LD)
+    sv, nu = _sv_nu_ld(invA, logSV0, sqrtPHI, svz, z)
+    E = LD(elb)
+
+    def step(x, shock):
+        xn = np.empty(K, LD)
+        xn[0] = x[0]
+        xn[1:1 + N] = P.T @ x + shock
+        xn[1 + N:] = x[1:K - N]
+        return xn
+
+    fY, fYc, yhat = np.empty((N, H, Nd)), np.empty((N, H, Nd)), np.empty((N, H))
+    gap = np.inf
+    for nn in range(Nd):
+        x = x0.copy()
+        for hh in range(H):
+            x = step(x, nu[:, hh, nn])
+            fY[:, hh, nn] = x[1:1 + N]
+        x = x0.copy()
+        for hh in range(H):
+            x = step(x, nu[:, hh, nn])
+            y = x[1:1 + N]  # a view: the floor goes into the state
+            gap = min(gap, float(np.min(np.abs(y[fl] - E))))
+            y[fl & (y < E)] = E
+            fYc[:, hh, nn] = y
+    x = x0.copy()
+    zero = np.zeros(N, LD)
+    for hh in range(H):
+        x = step(x, zero)
+        yhat[:, hh] = x[1:1 + N]
+    return fY, fYc, yhat, sv[:, 0, :], gap
+
+
+def gauss_logscore_ld(mu, S, y):
+    """logscoreGaussian.m:15-20 for N(mu, S S') in longdouble through chol_ld of S S' (any full-row-rank S)."""
+    S = np.asarray(S).astype(LD)
+    L = chol_ld(S @ S.T)
+    zz = fwd_ld(L, np.asarray(y).astype(LD) - np.asarray(mu).astype(LD))
+    n = L.shape[0]
+    return float(-(n * np.log(2 * LD(np.pi)) + 2 * np.sum(np.log(np.diag(L))) + zz @ zz) / 2)
+
+
+def fcst_scores_ld(PAI, invA, sv1, Xjumpoff, yrealized, ndxYields):
+    """The two uncensored one-step scores of mcmcVAR.m:326-332, 341-344 per draw: the full vector and the macro
+    block, N(muY, sqrtOmegaY sqrtOmegaY') with muY = PAI' Xjumpoff and sqrtOmegaY = invA diag(sv1(:, nn)).
+    Returns 2 x Nd."""
+    mu = np.asarray(PAI).astype(LD).T @ np.asarray(Xjumpoff).astype(LD)
+    x = ~np.asarray(ndxYields, bool)
+    out = np.empty((2, sv1.shape[1]))
+    for nn in range(sv1.shape[1]):
+        S = np.asarray(invA).astype(LD) * sv1[:, nn][None, :]
+        out[0, nn] = gauss_logscore_ld(mu, S, yrealized)
+        out[1, nn] = gauss_logscore_ld(mu[x], S[x, :], np.asarray(yrealized)[x])
+    return out
+
+
+def _shadow_sim_ld(Pshadow, Pactual, src, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, elb, svz, z):
+    """The simulation shared by the two shadow-rate models, on the explicit state [1, y(t) .. y(t-p+1)] and the
+    actual-rate state a = [a(t) .. a(t-p+1)] (blocks of len(src) rates): y <- Pshadow' x + Pactual' a + nu, the
+    shadow state shifted, a <- [max(y(src), ELB); a(1:end-block)].  Returns fY, fY with the yields floored
+    afterwards, sv1 and the smallest |y - ELB| over every comparison with the bound."""
+    K, N = Pshadow.shape
+    H, Nd = z.shape[1], z.shape[2]
+    yl = np.asarray(ndxYields, bool)
+    x0 = np.asarray(Xjumpoff).astype(LD)
+    sv, nu = _sv_nu_ld(invA, logSV0, sqrtPHI, svz, z)
+    E = LD(elb)
+    nb = len(src)
+    fY = np.empty((N, H, Nd))
+    gap = np.inf
+    for nn in range(Nd):
+        x, a = x0[:K].copy(), x0[K:].copy()
+        for hh in range(H):
+            y = Pshadow.T @ x + Pactual.T @ a + nu[:, hh, nn]
+            fY[:, hh, nn] = y
+            x = np.concatenate([x[:1], y, x[1:K - N]])
+            a = np.concatenate([np.maximum(y[src], E), a[:len(a) - nb]])
+            gap = min(gap, float(np.min(np.abs(y[yl] - E))))
+    fYc = fY.copy()
+    fYc[yl] = np.maximum(fYc[yl], float(elb))
+    return fY, fYc, sv[:, 0, :], gap
+
+
+def fcst_paths_bh_ld(PAI, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, actualrateBlock, elb, svz, z):
+    """mcmcVARshadowrateBlockHybrid.m:566-574, 611-625 for one kept draw in longdouble (arguments as
+    oracle.ccmm_oracle_fcst.fcst_draw_bh; Xjumpoff has K + Nyields p entries): the equations of
+    actualrateBlock read the yields' lags from the actual-rate states (PAIactual; PAIshadow is zero there), every
+    other coefficient multiplies the shadow state; the actual-rate state of a yield is max(shadow, ELB) (:623).
+    The yields of the returned censored paths are floored afterwards (:696-700)."""
+    P = np.asarray(PAI).astype(LD)
+    K, N = P.shape
+    p = (K - 1) // N
+    yl, act = np.asarray(ndxYields, bool), np.asarray(actualrateBlock, bool)
+    lag_rows = 1 + np.flatnonzero(np.tile(yl, p))  # ndxYIELDLAGS
+    Pact = P[lag_rows, :].copy()
+    Pact[:, ~act] = 0
+    Psh = P.copy()
+    Psh[np.ix_(lag_rows, np.flatnonzero(act))] = 0
+    return _shadow_sim_ld(Psh, Pact, np.flatnonzero(yl), invA, logSV0, sqrtPHI, Xjumpoff, yl, elb, svz, z)
+
+
+def fcst_paths_hybrid_ld(PAI, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, ndxSHADOWRATE, elb, svz, z):
+    """mcmcVARhybridGibbs.m:585, 621-635 for one kept draw in longdouble (arguments as
+    oracle.ccmm_oracle_fcst.fcst_draw_hybrid): PAI has Kshadow + Ns p rows, the last Ns p multiply the lags of
+    the actual rates max(shadow, ELB) of the Ns shadow-rate variables."""
+    P = np.asarray(PAI).astype(LD)
+    s = np.asarray(ndxSHADOWRATE, int)
+    N = P.shape[1]
+    p = (P.shape[0] - 1) // (N + s.size)
+    K = 1 + N * p
+    return _shadow_sim_ld(P[:K], P[K:], s, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, elb, svz, z)
+
+
+def fcst_mu_shadow_ld(PAI, Xjumpoff, ndxYields, actualrateBlock=None, ndxSHADOWRATE=None):
+    """muY = fcstA(ndxfcstY, :) Xjumpoff of the block-hybrid (:566-584) or hybrid (:585, 591-595) model."""
+    P = np.asarray(PAI).astype(LD)
+    x = np.asarray(Xjumpoff).astype(LD)
+    if ndxSHADOWRATE is not None:
+        return P.T @ x
+    K, N = P.shape
+    p = (K - 1) // N
+    yl, act = np.asarray(ndxYields, bool), np.asarray(actualrateBlock, bool)
+    lag_rows = 1 + np.flatnonzero(np.tile(yl, p))
+    Pact = P[lag_rows, :].copy()
+    Pact[:, ~act] = 0
+    Psh = P.copy()
+    Psh[np.ix_(lag_rows, np.flatnonzero(act))] = 0
+    return Psh.T @ x[:K] + Pact.T @ x[K:]

@@ -2,12 +2,15 @@
 headers (ccmm_elb.h, ccmm_sweep.h, ccmm_fcst.h, ccmm_lag.h), calls no HIP runtime function and prints the plans
 and LDS layouts the host launchers use.  Checked against the restatements of tests/elb_cases.py on every ELB
 edge case, so that the edge asserts there (n65_lagbatch -> kb 10, long_w4 -> 4, long_w1 -> 1) are statements
-about the library, and against the layout comments of the kernels region by region."""
+about the library, and against the layout comments of the kernels region by region.  The predictive-density
+launch (fcst_reg_path, fcst_chunk, fcst_variant, fcst_paths_lds_doubles) is checked on every case of
+tests/fcst_cases.py in the same way."""
 import subprocess
 
 import pytest
 
 import elb_cases as EC
+import fcst_cases as FC
 from conftest import ROOT
 
 CSRC = ROOT / "ccmmshadowratevar-code_amd" / "csrc"
@@ -137,3 +140,36 @@ def test_prep_and_sweep_plans(plans):
     assert r32[2] == -1 and r32[4] == 0 and r32[3] == 4 * 32 * 33 * 8
     assert all(r[1] <= LDS_CU and r[3] <= LDS_CU and r[5:7] == [1, 1] for r in (r20, r32, r8, r9))
     assert (r8[7], r32[7]) == (1, 0)  # the lag solve's resident design: N = 8 at TP = 96 fits, N = 32 at 768 does not
+
+
+def test_fcst_plans_match_the_restatement(plans):
+    """Every shape case of tests/fcst_cases.py: fcst_reg_path, fcst_chunk in both forms, the k_fcst<RN> instance
+    and the chunk and LDS bytes launch_fcst takes, with option fcst_reg on and off; then the variant table of
+    tests/test_gpu_fcst_edges.py's docstring, as statements about the library."""
+    cases = list(FC.CASES.values())
+    q = [(c, opt) for c in cases for opt in (1, 0)]
+    got = {}
+    for (c, opt), row in zip(q, plans([f"fcst {c.N} {c.p} {c.H} 0 {opt}" for c, opt in q])):
+        r = list(map(int, row))
+        Kx = c.N * c.p + 1
+        reg = FC.reg_path(c.N, c.p) and bool(opt)
+        hc = FC.chunk(c.N, Kx, c.p, c.H, reg)
+        assert r == [int(FC.reg_path(c.N, c.p)), FC.chunk(c.N, Kx, c.p, c.H, True), FC.chunk(c.N, Kx, c.p, c.H, False),
+                     FC.variant(c.N, c.p, 0, bool(opt)), hc, FC.paths_lds_doubles(c.N, Kx, c.p, hc, reg) * 8], (c.name, opt)
+        assert r[5] <= LDS_CU, c.name
+        got[c.name, opt] = (r[3], r[4])
+    rn = {n: got[n, 1][0] for n in FC.CASES}
+    assert [n for n in rn if rn[n] == 20] == ["n2_p2", "n16_p3", "n20_p4_h17", "h15", "h33", "nd1"]
+    assert [n for n in rn if rn[n] == 21] == ["n3_p1", "n19_p5", "n21_p12_h16", "h1"]
+    assert [n for n in rn if rn[n] == 0] == ["n22_p2", "n31_p3", "n32_p1", "n8_p13", "n21_p13", "n32_p15_h25"]
+    assert all(got[n, 0][0] == 0 for n in FC.CASES)  # fcst_reg = 0: always PAI in LDS
+    assert got["n32_p15_h25", 1] == (0, 13) and FC.chunks(32, 15, 25) == [13, 12]  # 25 does not fit, 13 does
+    assert FC.chunks(20, 4, 17) == [16, 1] and FC.chunks(4, 2, 33) == [16, 16, 1] and FC.chunks(21, 12, 16) == [16]
+    assert FC.chunks(6, 3, 15) == [15] and FC.chunks(5, 2, 1) == [1]
+    assert FC.chunks(20, 4, 17, reg_opt=False) == [17]  # the LDS form takes the horizons whole
+    # the hybrid model never takes the register path; the refused shape does not fit at one horizon per chunk
+    assert plans(["fcst 8 2 5 2 1"])[0][:1] == ["0"] and plans(["fcst 8 2 5 2 1"])[0][3] == "0"
+    r = list(map(int, plans(["fcst 32 19 1 0 1"])[0]))
+    assert r[4] == 1 and r[5] > LDS_CU
+    # no register-path shape is refused by the drop-in's LDS check (made with the LDS form): the largest fits
+    assert FC.paths_lds_doubles(21, 253, 12, 1) * 8 <= LDS_CU

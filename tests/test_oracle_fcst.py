@@ -137,3 +137,94 @@ def test_bh_forecast_actual_rates(F, oracle, fred):
             ym[yields] = np.maximum(ym[yields], elb)
             mixed = [ym] + mixed[:-1]
     assert np.all(np.isfinite(sc))
+
+
+# =============================================================================================
+# The censored log scores on the structured grid of tests/mvncdf_grid.py against 40-digit values
+# (tests/golden/mvncdf_grid.npz, written by tests/golden/make_mvncdf_grid.py).
+import mvncdf_grid as G  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def grid():
+    return G.load()
+
+
+def test_mvncdf_grid_fixture_matches_the_generator(grid):
+    """The committed inputs are those of mvncdf_grid.slabs(), and every tenth point's 40-digit values are
+    reproduced."""
+    for n in G.slabs():
+        for k, v in G.slab_arrays(n).items():
+            np.testing.assert_array_equal(grid[n][k], v, err_msg=f"{n} {k}")
+    pts = G.all_points()
+    for n, i in pts[::10]:
+        got = G.truth(n, i)
+        want = tuple(grid[n][k][i] for k in ("t1", "t3", "P1", "P3", "u1", "u3"))
+        assert got == tuple(float(w) if j < 4 else bool(w) for j, w in enumerate(want)), (n, i)
+    # the edges the grid was built for are in it
+    d1 = grid["d1"]
+    assert d1["u3"].sum() == 2 and np.any((d1["P3"] > 0) & (d1["P3"] < 2.3e-308))  # underflow, and a subnormal
+    P = np.concatenate([grid["d2a"]["P3"], grid["d2b"]["P3"]])
+    assert np.any((P > 0) & (P < 1e-100)) and np.any(P > 0.99)
+
+
+def test_trivariate_truth_against_the_one_factor_integral():
+    """Plackett's reduction (the d = 3 truth) against the one-factor integral on covariances D + lam lam' with
+    every correlation non-zero and both signs: two independent forms of the same probability."""
+    import mpmath as mp
+    with mp.workdps(G.DPS):
+        for D, lam, x in (([0.5, 0.7, 0.4], [0.6, -0.9, 1.1], [0.3, -0.2, 0.8]),
+                          ([0.2, 0.3, 0.05], [1.0, 0.8, 1.5], [-2.5, -1.0, -3.0])):
+            L = np.linalg.cholesky(np.diag(D) + np.outer(lam, lam))
+            # the factor is rounded to fp64: compare on the covariance it stands for
+            Lm = [[mp.mpf(float(L[i][j])) for j in range(3)] for i in range(3)]
+            S = [[sum(Lm[i][k] * Lm[j][k] for k in range(3)) for j in range(3)] for i in range(3)]
+            l1 = mp.sqrt(S[0][1] * S[0][2] / S[1][2])
+            lm = [l1, S[0][1] / l1, S[0][2] / l1]
+            a = G.cdf3_mp([mp.mpf(v) for v in x], Lm)
+            b = G.onefactor_mp(x, [S[i][i] - lm[i] ** 2 for i in range(3)], lm)
+            assert abs(a - b) < mp.mpf(10) ** -30 * b, (a, b)
+
+
+@pytest.mark.parametrize("slab", ["d1", "d2a", "d2b", "d3"] + [f"{k}_{n}" for n in (1, 2, 3) for k in ("q1", "q3", "c2")])
+def test_oracle_on_the_grid_low_dimensions(grid, slab):
+    """The oracle (normcdf exactly, scipy quad for two and three series) at the project's log-score tolerances
+    against truth; the points it misses are those of G.ORACLE_MISSES, at most a tenth of the d <= 3 grid."""
+    a = grid[slab]
+    s1, s3 = G.oracle_scores(a)
+    e = np.maximum(G.score_err(s1, a["t1"], a["u1"]), G.score_err(s3, a["t3"], a["u3"]))
+    listed = np.array([n in G.ORACLE_MISSES for n in a["names"]])
+    print(f"{slab}: oracle vs truth {e[~listed].max():.2e} off the list, {int(listed.sum())} listed")
+    bad = [(str(a["names"][i]), float(e[i])) for i in np.nonzero(~listed & (e >= G.tol_of(slab)))[0]]
+    assert not bad, bad
+    assert not np.any(np.isnan(s1)) and not np.any(np.isnan(s3))
+
+
+def test_oracle_miss_list_is_within_its_cap(grid):
+    names = np.concatenate([grid[n]["names"] for n in ("d1", "d2a", "d2b", "d3")])
+    assert set(G.ORACLE_MISSES) <= set(names)
+    assert len(G.ORACLE_MISSES) <= G.MISS_CAP * names.size
+
+
+@pytest.mark.parametrize("slab", [f"lat{d}" for d in range(4, 13)] + ["c2_4"])
+def test_oracle_lattice_rule_on_the_grid(grid, slab):
+    """The declared lattice rule against the one-factor truth: inside MATLAB's 1e-4 on the probability."""
+    a = grid[slab]
+    s1, s3 = G.oracle_scores(a)
+    for got, t, P in ((s1, a["t1"], a["P1"]), (s3, a["t3"], a["P3"])):
+        pe = np.abs(np.exp(got - (t - np.log(P))) - P)
+        print(f"{slab}: lattice rule vs truth {pe.max():.2e} on the probability")
+        assert pe.max() < G.LAT_ABS
+
+
+def test_lattice_generators_in_the_kernel_source_are_the_oracles(F):
+    """The generators of the device's lattice rule, read from csrc/ccmm_fcst.hip, are the fp64 square roots of
+    the primes the oracle uses, digit for digit: a generator one ulp off moves the rule by 2e-12, the size of the
+    rounding differences between device and oracle and far inside the 1e-8 at which they are compared."""
+    import re
+    from conftest import ROOT
+    src = (ROOT / "ccmmshadowratevar-code_amd" / "csrc" / "ccmm_fcst.hip").read_text()
+    body = re.search(r"const double alpha\[kMvnMaxD - 1\] = \{([^}]*)\}", src).group(1)
+    alpha = np.array([float(t) for t in body.replace("\n", " ").split(",")])
+    np.testing.assert_array_equal(alpha, F.MVN_ALPHA)
+    assert int(re.search(r"kMvnPts = 64 \* (\d+)", src).group(1)) * 64 == F.MVN_PTS

@@ -168,3 +168,82 @@ def test_truncnorm_host_vs_mpmath(pkg):
     res = np.array([pkg._abi.draw_trunc_normal(mu[i], sig[i], tg.ELB, u[i]) for i in range(mu.size)])
     err = tg.compare(res[:, 0], res[:, 1], "host")
     assert err < tg.C_BOUND, err
+
+
+# =============================================================================================
+# The predictive-density block: the shape cases of tests/fcst_cases.py (tests/test_gpu_fcst_edges.py holds the
+# device to 1e-9 of refs.fcst_paths_ld on them).
+#
+# Measured, oracle.ccmm_oracle_fcst.fcst_draw against the longdouble restatement in units of max(|x|, 1):
+# paths and mean path 6.8e-15 at worst (n32_p15_h25), the two uncensored scores 2.8e-15; BOUND = 1e-11 holds
+# with three orders of headroom.  Smallest |y - ELB| at a floor comparison: 3.7e-5 (n32_p15_h25).
+import fcst_cases as fcc  # noqa: E402
+
+
+@pytest.mark.parametrize("name", list(fcc.CASES))
+def test_fcst_oracle_vs_longdouble(name):
+    c, d = fcc.CASES[name], fcc.linear_inputs(name)
+    floored = 0
+    for ch, ((fY, fYc, yhat, sc, gap), orc) in enumerate(zip(fcc.longdouble_reference(name), fcc.oracle_reference(name))):
+        r = fcc.spectral_radius(d["PAI"][..., ch], c.N, c.p)
+        e = max(rel_err(orc[0], fY, 1.0), rel_err(orc[1], fYc, 1.0), rel_err(orc[2], yhat, 1.0))
+        es = rel_err(orc[3][[0, 2]], sc, 1.0)
+        print(f"fcst {name} chain {ch}: radius {r:.3f}, oracle vs longdouble paths {e:.2e} scores {es:.2e}, "
+              f"closest floor comparison {gap:.1e}")
+        assert r <= 0.95
+        assert e < BOUND and es < BOUND, (e, es)
+        assert gap >= 1e-7  # no floor decision within rounding of the bound: the flags compare exactly
+        fl = fYc[d["yields"]] == d["elb"]
+        np.testing.assert_array_equal(fl, orc[1][d["yields"]] == d["elb"])
+        floored += int(fl.sum())
+        assert not fl.all()
+    assert floored > 0  # the floor binds somewhere and not everywhere
+    assert int(np.sum(d["y"][d["yields"]] <= d["elb"])) == c.nat
+
+
+def test_fcst_cases_cover_the_launch_decisions():
+    """Every k_fcst instance, both lane-group layouts, fewer lags than lane groups, the last register slot, every
+    chunk pattern of the issue's table, one forecast draw, yields in the first and the last position."""
+    C = fcc.CASES
+    assert {fcc.variant(c.N, c.p) for c in C.values()} == {0, 20, 21}
+    assert {c.N for c in C.values() if fcc.variant(c.N, c.p) == 20} >= {2, 16, 20}
+    assert {c.N for c in C.values() if fcc.variant(c.N, c.p) == 21} >= {3, 19, 21}
+    assert {c.N for c in C.values() if fcc.variant(c.N, c.p) == 0 and c.p <= 12} == {22, 31, 32}
+    assert {c.N for c in C.values() if c.p == 13} == {8, 21}
+    assert {c.p for c in C.values()} >= {1, 2, 3, 4, 5, 12, 13}
+    assert any(c.p < fcc.lane_groups(c.N) for c in C.values() if c.N <= 21)
+    assert any(c.p < fcc.lane_groups(c.N) for c in C.values() if c.N > 21)
+    assert {c.H for c in C.values() if fcc.reg_path(c.N, c.p)} >= {1, 15, 16, 17, 33}
+    assert fcc.chunks(32, 15, 25) == [13, 12]
+    assert any(c.Nd == 1 for c in C.values())
+    assert any(0 in c.yields for c in C.values()) and any(c.N - 1 in c.yields for c in C.values())
+    assert fcc.variant(*[getattr(C[fcc.REG_OPTION_CASE], k) for k in ("N", "p")]) == 20
+
+
+@pytest.mark.parametrize("name", list(fcc.CASES))
+def test_fcst_shadow_rate_oracles_vs_longdouble(name):
+    """fcst_draw_bh and fcst_draw_hybrid (dense companions as written) against refs.fcst_paths_bh_ld /
+    fcst_paths_hybrid_ld on the draws of every shape case; measured 2.4e-15 at worst (n32_p15_h25)."""
+    import refs
+    from oracle import ccmm_oracle_fcst as F
+    d = fcc.linear_inputs(name)
+    rest = (d["yields"],)
+    args, actual = fcc.bh_inputs(name)
+    fY, _ = F.fcst_draw_bh(*args, d["y"], d["yields"], actual, d["elb"], d["svz"][..., 0], d["z"][..., 0])
+    ld = refs.fcst_paths_bh_ld(*args, d["yields"], actual, d["elb"], d["svz"][..., 0], d["z"][..., 0])
+    e_bh = rel_err(fY, ld[0], 1.0)
+    args, s = fcc.hybrid_inputs(name)
+    fY, _ = F.fcst_draw_hybrid(*args, d["y"], d["yields"], s, d["elb"], d["svz"][..., 0], d["z"][..., 0])
+    lh = refs.fcst_paths_hybrid_ld(*args, d["yields"], s, d["elb"], d["svz"][..., 0], d["z"][..., 0])
+    e_hy = rel_err(fY, lh[0], 1.0)
+    print(f"fcst {name}: block hybrid {e_bh:.2e}, hybrid {e_hy:.2e} vs longdouble; floor gaps {ld[3]:.1e} {lh[3]:.1e}")
+    assert e_bh < BOUND and e_hy < BOUND, (e_bh, e_hy)
+    assert np.any(ld[0][d["yields"]] < d["elb"]) and np.any(lh[0][s] < d["elb"])  # the actual-rate floor binds
+
+
+def test_fcst_chain_cases_cover_the_variants():
+    v = {n: fcc.chain_variant(n) for n in fcc.CHAIN_CASES}
+    assert (v["bh_n6_p2"], v["bh_n7_p3"], v["bh_n5_p13"]) == (20, 21, 0)
+    assert all(v[n] == 0 for n in v if n.startswith("hy_"))
+    assert {len(c[2]) for n, c in fcc.CHAIN_CASES.items() if n.startswith("hy_")} == {1, 4, 5}
+    assert all(c[5] <= 17 and c[6] <= 3 for c in fcc.CHAIN_CASES.values())
