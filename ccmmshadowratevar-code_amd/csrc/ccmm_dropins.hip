@@ -446,7 +446,10 @@ static int girf_impl(ccmm_ctx* ctx, int M, int N, int p, int H, int nsim, const 
     require(bh == 0 || Ny >= 1, "no ring variables");
     const int ldX = K + Ny * p;
     const int ldP = (bh == 2) ? ldX : K;
-    require((K + Ny * p + N + 3) / 4 <= 96, "state too large for the GIRF kernel (K + Ny p + N <= 384)");
+    const GirfPlan plan = girf_plan(N, p, Ny, ctx->opt[OPT_GIRF_GENERIC] != 0);
+    require(plan.nks <= kGirfMaxKs, "state too large for the GIRF kernel (K + Ny p + N <= 384)");
+    // (the table-driven kernel keeps p rows of the state's row table beside the state: many lags of few variables)
+    require(plan.lds <= kLdsCu, "the GIRF state and its row table do not fit LDS (p (K + Ny p + N) ints + the state)");
     const size_t nch = (size_t)(nsim + 3) / 4;
     DBuf<double> dPAI, dA, dS, dSV, dX, dZ, dSZ, dPart, dOut;
     DBuf<uint8_t> dAct, dCum, dFl;

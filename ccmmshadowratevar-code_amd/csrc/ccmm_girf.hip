@@ -23,7 +23,7 @@ namespace ccmm {
 
 namespace {
 
-constexpr int kGS = 16;  // simulations per workgroup: 4 paths x 4 antithetic shock sets
+constexpr int kGS = kGirfSims;
 
 struct GirfDev {
   int M, N, p, H, nsim, bh, Ny, KX, KT, nchunk;
@@ -394,11 +394,6 @@ __global__ void k_girf_reduce(int M, int N, int H, int nchunk, int nsim, const d
 
 }  // namespace
 
-size_t girf_lds_bytes(int N, int p, int KT) {
-  const int nks = (KT + 3) / 4;
-  return ((size_t)nks * 4 * kGS + 12 * N + (size_t)N * kGS) * sizeof(double) + (size_t)p * nks * 4 * sizeof(int);
-}
-
 hipError_t girf_launch(hipStream_t st, const GirfArgs& a) {
   GirfDev g{};
   g.M = a.M; g.N = a.N; g.p = a.p; g.H = a.H; g.nsim = a.nsim; g.bh = a.bh; g.Ny = a.bh ? a.Ny : 0;
@@ -411,30 +406,21 @@ hipError_t girf_launch(hipStream_t st, const GirfArgs& a) {
   g.PAI = a.PAI; g.invA = a.invA; g.sqrtPHI = a.sqrtPHI; g.SV0 = a.SV0; g.Xj = a.Xj; g.ldX = a.ldX;
   g.actual = a.actual; g.yidx = a.yidx; g.elb = a.elb; g.shock11 = a.shock11; g.z = a.z; g.svz = a.svz;
   g.seed = a.seed; g.part = a.part;
-  const int nks = (g.KT + 3) / 4;
-  const size_t lds = girf_lds_bytes(a.N, a.p, g.KT);
-  const dim3 grid(g.nchunk, 3, a.M), block(64 * ((a.N + 15) / 16));
+  const GirfPlan pl = girf_plan(a.N, a.p, g.Ny, a.force_generic != 0);
+  const dim3 grid(g.nchunk, 3, a.M), block(pl.threads);
   auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, block, lds, st, g);
+    hipError_t e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+    if (e2 != hipSuccess) return e2;
+    hipLaunchKernelGGL(kern, grid, block, pl.lds, st, g);
     return hipGetLastError();
   };
   hipError_t e;
-  const int N4 = (a.N + 3) / 4 * 4, NY4 = (g.Ny + 3) / 4 * 4;
-  const size_t lds_fast = ((size_t)(a.p * (N4 + NY4) + N4 + 4) * kGS + 12 * a.N + (size_t)a.N * kGS) * sizeof(double);
-  auto go_fast = [&](auto kern) -> hipError_t {
-    hipError_t e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast);
-    if (e2 != hipSuccess) return e2;
-    hipLaunchKernelGGL(kern, grid, block, lds_fast, st, g);
-    return hipGetLastError();
-  };
-  if (!a.force_generic && a.p == 12 && N4 == 20 && NY4 == 8) e = go_fast(k_girf_fast<12, 20, 8>);
-  else if (!a.force_generic && a.p == 12 && N4 == 20 && NY4 == 4) e = go_fast(k_girf_fast<12, 20, 4>);
-  else if (!a.force_generic && a.p == 12 && N4 == 20 && NY4 == 0) e = go_fast(k_girf_fast<12, 20, 0>);
-  else if (nks <= 32) e = go(k_girf<32>);
-  else if (nks <= 64) e = go(k_girf<64>);
-  else if (nks <= 96) e = go(k_girf<96>);
+  if (pl.fast_ny4 == 8) e = go(k_girf_fast<kGirfFastP, kGirfFastN4, 8>);
+  else if (pl.fast_ny4 == 4) e = go(k_girf_fast<kGirfFastP, kGirfFastN4, 4>);
+  else if (pl.fast_ny4 == 0) e = go(k_girf_fast<kGirfFastP, kGirfFastN4, 0>);
+  else if (pl.ks == 32) e = go(k_girf<32>);
+  else if (pl.ks == 64) e = go(k_girf<64>);
+  else if (pl.ks == 96) e = go(k_girf<96>);
   else return hipErrorInvalidValue;
   if (e != hipSuccess) return e;
   const int nt = a.N * 3 * a.M;

@@ -11,11 +11,17 @@
 //   misc N K KP TP dPHI        -> n_bucket, the A-step and PHI plans, whether the other kernels' LDS fits a CU
 //   fcst N p H bh reg_opt      -> fcst_reg_path, fcst_chunk (register form, LDS form), the k_fcst<RN> instance and the
 //                                 chunk and LDS bytes launch_fcst takes with option fcst_reg = reg_opt (Kx = N p + 1)
+//   girf N p Ny generic        -> girf_plan: fast NY4 (-1: table-driven), k_girf<KS> bucket, nks, threads, LDS bytes
+//   girfg N p nks              -> bytes, then name:offset of every region of k_girf<KS>
+//   girff N NY4                -> the same for k_girf_fast<12, 20, NY4>
+//   philox idx chain sweep block seedlo seedhi -> the four output words (hex) of Rng::raw(block, idx >> 1), the
+//                                 counter and key of the library's Philox4x32-10 normals and uniforms
 #include <cstdio>
 #include <cstring>
 
 #include "ccmm_elb.h"
 #include "ccmm_fcst.h"
+#include "ccmm_girf.h"
 #include "ccmm_lag.h"
 #include "ccmm_sweep.h"
 
@@ -29,6 +35,7 @@ static void wave(const ElbWaveLds& l) {
 int main() {
   char cmd[16];
   int a, b, c, d, e;
+  unsigned u[6];
   while (std::scanf("%15s", cmd) == 1) {
     if (!std::strcmp(cmd, "cond") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
       const ElbCondPlan pl = elb_cond_plan(a, b, c);
@@ -65,6 +72,22 @@ int main() {
       std::printf("%d %d %d %d %d %zu\n", (int)fcst_reg_path(a, b, d), fcst_chunk(a, Kx, b, c, true),
                   fcst_chunk(a, Kx, b, c, false), fcst_variant(a, b, d, e != 0), hc,
                   fcst_paths_lds_doubles(a, Kx, b, hc, reg) * sizeof(double));
+    } else if (!std::strcmp(cmd, "girf") && std::scanf("%d %d %d %d", &a, &b, &c, &d) == 4) {
+      const GirfPlan pl = girf_plan(a, b, c, d != 0);
+      std::printf("%d %d %d %d %zu\n", pl.fast_ny4, pl.ks, pl.nks, pl.threads, pl.lds);
+    } else if (!std::strcmp(cmd, "girfg") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
+      const GirfLds l = girf_lds(a, b, c);
+      std::printf("%zu X:%zu logsv:%zu ybuf:%zu nrm:%zu rowtab:%zu\n", l.end, l.X, l.logsv, l.ybuf, l.nrm, l.rowtab);
+    } else if (!std::strcmp(cmd, "girff") && std::scanf("%d %d", &a, &b) == 2) {
+      const GirfLds l = girf_fast_lds(a, kGirfFastP, kGirfFastN4, b);
+      std::printf("%zu X:%zu logsv:%zu ybuf:%zu nrm:%zu\n", l.end, l.X, l.logsv, l.ybuf, l.nrm);
+    } else if (!std::strcmp(cmd, "philox") && std::scanf("%u %u %u %u %u %u", &u[0], &u[1], &u[2], &u[3], &u[4], &u[5]) == 6) {
+      Rng rng{};
+      rng.seed = ((uint64_t)u[5] << 32) | u[4];
+      rng.chain = u[1];
+      rng.sweep = u[2];
+      const u32x4 r = rng.raw((int)u[3], u[0] >> 1);
+      std::printf("%08x %08x %08x %08x\n", r.x, r.y, r.z, r.w);
     } else {
       std::fprintf(stderr, "bad query: %s\n", cmd);
       return 2;

@@ -293,19 +293,17 @@ def fcst_scores_ld(PAI, invA, sv1, Xjumpoff, yrealized, ndxYields):
     return out
 
 
-def _shadow_sim_ld(Pshadow, Pactual, src, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, elb, svz, z):
-    """The simulation shared by the two shadow-rate models, on the explicit state [1, y(t) .. y(t-p+1)] and the
-    actual-rate state a = [a(t) .. a(t-p+1)] (blocks of len(src) rates): y <- Pshadow' x + Pactual' a + nu, the
-    shadow state shifted, a <- [max(y(src), ELB); a(1:end-block)].  Returns fY, fY with the yields floored
-    afterwards, sv1 and the smallest |y - ELB| over every comparison with the bound."""
+def _shadow_core_ld(Pshadow, Pactual, src, x0, nu, elb, yl):
+    """The simulation core of the shadow-rate models for given reduced-form shocks nu (N x H x Nd, longdouble),
+    on the explicit state x = [1, y(t) .. y(t-p+1)] and the actual-rate state a = [a(t) .. a(t-p+1)] (blocks of
+    len(src) rates; none for the linear model): y <- Pshadow' x + Pactual' a + nu, the shadow state shifted,
+    a <- [max(y(src), ELB); a(1:end-block)].  Returns the unfloored paths (N x H x Nd, longdouble) and the
+    smallest |y(yl) - ELB| over every path and horizon (inf when yl selects nothing)."""
     K, N = Pshadow.shape
-    H, Nd = z.shape[1], z.shape[2]
-    yl = np.asarray(ndxYields, bool)
-    x0 = np.asarray(Xjumpoff).astype(LD)
-    sv, nu = _sv_nu_ld(invA, logSV0, sqrtPHI, svz, z)
+    H, Nd = nu.shape[1], nu.shape[2]
     E = LD(elb)
     nb = len(src)
-    fY = np.empty((N, H, Nd))
+    fY = np.empty((N, H, Nd), LD)
     gap = np.inf
     for nn in range(Nd):
         x, a = x0[:K].copy(), x0[K:].copy()
@@ -314,10 +312,37 @@ def _shadow_sim_ld(Pshadow, Pactual, src, invA, logSV0, sqrtPHI, Xjumpoff, ndxYi
             fY[:, hh, nn] = y
             x = np.concatenate([x[:1], y, x[1:K - N]])
             a = np.concatenate([np.maximum(y[src], E), a[:len(a) - nb]])
-            gap = min(gap, float(np.min(np.abs(y[yl] - E))))
+            if yl.any():
+                gap = min(gap, float(np.min(np.abs(y[yl] - E))))
+    return fY, gap
+
+
+def _shadow_sim_ld(Pshadow, Pactual, src, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, elb, svz, z):
+    """The simulation shared by the two shadow-rate models (_shadow_core_ld) on the shocks of one kept draw
+    (_sv_nu_ld).  Returns fY, fY with the yields floored afterwards, sv1 and the smallest |y - ELB| over every
+    comparison with the bound."""
+    yl = np.asarray(ndxYields, bool)
+    x0 = np.asarray(Xjumpoff).astype(LD)
+    sv, nu = _sv_nu_ld(invA, logSV0, sqrtPHI, svz, z)
+    fYl, gap = _shadow_core_ld(Pshadow, Pactual, src, x0, nu, elb, yl)
+    fY = fYl.astype(np.float64)
     fYc = fY.copy()
     fYc[yl] = np.maximum(fYc[yl], float(elb))
     return fY, fYc, sv[:, 0, :], gap
+
+
+def _bh_split_ld(P, yl, act):
+    """PAIshadow / PAIactual of the block-hybrid model (mcmcVARshadowrateBlockHybrid.m:566-574;
+    generateGIRF2blockhybrid.m:226-234): the equations of ``act`` read the yields' lags from the actual-rate
+    states, every other coefficient multiplies the shadow state."""
+    K, N = P.shape
+    p = (K - 1) // N
+    lag_rows = 1 + np.flatnonzero(np.tile(yl, p))  # ndxYIELDLAGS
+    Pact = P[lag_rows, :].copy()
+    Pact[:, ~act] = 0
+    Psh = P.copy()
+    Psh[np.ix_(lag_rows, np.flatnonzero(act))] = 0
+    return Psh, Pact
 
 
 def fcst_paths_bh_ld(PAI, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, actualrateBlock, elb, svz, z):
@@ -327,14 +352,8 @@ def fcst_paths_bh_ld(PAI, invA, logSV0, sqrtPHI, Xjumpoff, ndxYields, actualrate
     other coefficient multiplies the shadow state; the actual-rate state of a yield is max(shadow, ELB) (:623).
     The yields of the returned censored paths are floored afterwards (:696-700)."""
     P = np.asarray(PAI).astype(LD)
-    K, N = P.shape
-    p = (K - 1) // N
     yl, act = np.asarray(ndxYields, bool), np.asarray(actualrateBlock, bool)
-    lag_rows = 1 + np.flatnonzero(np.tile(yl, p))  # ndxYIELDLAGS
-    Pact = P[lag_rows, :].copy()
-    Pact[:, ~act] = 0
-    Psh = P.copy()
-    Psh[np.ix_(lag_rows, np.flatnonzero(act))] = 0
+    Psh, Pact = _bh_split_ld(P, yl, act)
     return _shadow_sim_ld(Psh, Pact, np.flatnonzero(yl), invA, logSV0, sqrtPHI, Xjumpoff, yl, elb, svz, z)
 
 
@@ -365,3 +384,60 @@ def fcst_mu_shadow_ld(PAI, Xjumpoff, ndxYields, actualrateBlock=None, ndxSHADOWR
     Psh = P.copy()
     Psh[np.ix_(lag_rows, np.flatnonzero(act))] = 0
     return Psh.T @ x[:K] + Pact.T @ x[K:]
+
+
+# ------------------------------------------------------------------ generalized impulse responses (tests/girf_cases.py)
+def girf_ld(PAI, invA, sqrtPHI, SV0, Xjumpoff, z, svz, shock11, cumcode, np_, model="linear", actual=None,
+            yields=None, shadow=None, elb=0.25):
+    """generateGIRF2linear.m / generateGIRF2blockhybrid.m:199-259 / generateGIRF2hybrid.m:191-251 for one kept
+    draw in longdouble, on the explicit state of _shadow_core_ld (no companion matrix).  z, svz: N x H x nsim.
+    antitheticSim: SV = exp(cumsum(sqrtPHI svz, 2) / 2) and the four shock sets z SV SV0, -z SV SV0, z / SV SV0,
+    -z / SV SV0, each with the scenario's shock (0, +shock11, -shock11) added to element (1, 1) before invA.
+    model "bh": PAIshadow / PAIactual of ``actual`` and ``yields`` (the ring holds the yields); "hybrid": PAI has
+    K + Ns p rows, the last Ns p multiply the lags of the actual rates of ``shadow``.  The ring takes max(y, ELB);
+    the yields are floored in the output only.  Mean over the 4 nsim paths, then cumsum / np_ for ``cumcode``.
+
+    Returns the three mean paths (3 x N x H, longdouble), the share of yield values (all paths, horizons and
+    scenarios) below the ELB (nan for the linear model) and the smallest |y - ELB| over all of them."""
+    P = np.asarray(PAI).astype(LD)
+    N, H, nsim = z.shape
+    if model == "hybrid":
+        src = np.flatnonzero(np.asarray(shadow, bool))
+        p = (P.shape[0] - 1) // (N + src.size)
+        K = 1 + N * p
+        Psh, Pact = P[:K], P[K:]
+        yl = np.asarray(yields, bool)
+    elif model == "bh":
+        yl = np.asarray(yields, bool)
+        Psh, Pact = _bh_split_ld(P, yl, np.asarray(actual, bool))
+        src = np.flatnonzero(yl)
+    else:
+        assert model == "linear"
+        Psh, Pact, src, yl = P, np.zeros((0, N), LD), np.zeros(0, int), np.zeros(N, bool)
+    x0 = np.asarray(Xjumpoff).astype(LD)
+    assert x0.size == Psh.shape[0] + Pact.shape[0]
+    zl = np.asarray(z).astype(LD)
+    SV = np.exp(np.cumsum(np.einsum("ij,jhn->ihn", np.asarray(sqrtPHI).astype(LD), np.asarray(svz).astype(LD)),
+                          axis=1) / 2)
+    s0 = np.asarray(SV0).astype(LD)[:, None, None]
+    iA = np.asarray(invA).astype(LD)
+    cc = np.zeros(N, bool) if cumcode is None else np.asarray(cumcode, bool)
+    E = LD(elb)
+    out = np.empty((3, N, H), LD)
+    below = total = 0
+    gap = np.inf
+    for sc, s11 in enumerate((LD(0), LD(shock11), -LD(shock11))):
+        sets = []
+        for sign, up in ((1, True), (-1, True), (1, False), (-1, False)):
+            eps = sign * zl * (SV if up else 1 / SV) * s0
+            eps[0, 0, :] += s11
+            sets.append(np.einsum("ij,jhn->ihn", iA, eps))
+        fY, g = _shadow_core_ld(Psh, Pact, src, x0, np.concatenate(sets, axis=2), elb, yl)
+        gap = min(gap, g)
+        below += int(np.sum(fY[yl] < E))
+        total += fY[yl].size
+        fY[yl] = np.maximum(fY[yl], E)
+        m = np.sum(fY, axis=2) / (4 * nsim)
+        m[cc] = np.cumsum(m[cc], axis=1) / LD(np_)
+        out[sc] = m
+    return out, (below / total if total else float("nan")), gap

@@ -4,13 +4,17 @@ and LDS layouts the host launchers use.  Checked against the restatements of tes
 edge case, so that the edge asserts there (n65_lagbatch -> kb 10, long_w4 -> 4, long_w1 -> 1) are statements
 about the library, and against the layout comments of the kernels region by region.  The predictive-density
 launch (fcst_reg_path, fcst_chunk, fcst_variant, fcst_paths_lds_doubles) is checked on every case of
-tests/fcst_cases.py in the same way."""
+tests/fcst_cases.py in the same way, and the GIRF launch (ccmm_girf.h girf_plan, girf_lds, girf_fast_lds) on every
+case of tests/girf_cases.py.  The same program prints the library's Philox4x32-10 words (Rng::raw), which pin
+tests/philox.py bit for bit."""
 import subprocess
 
 import pytest
 
 import elb_cases as EC
 import fcst_cases as FC
+import girf_cases as GC
+import philox
 from conftest import ROOT
 
 CSRC = ROOT / "ccmmshadowratevar-code_amd" / "csrc"
@@ -173,3 +177,82 @@ def test_fcst_plans_match_the_restatement(plans):
     assert r[4] == 1 and r[5] > LDS_CU
     # no register-path shape is refused by the drop-in's LDS check (made with the LDS form): the largest fits
     assert FC.paths_lds_doubles(21, 253, 12, 1) * 8 <= LDS_CU
+
+
+def test_girf_plans_match_the_case_table(plans):
+    """Every case of tests/girf_cases.py takes the kernel its table entry names (the table of
+    tests/test_gpu_girf_edges.py's docstring), with the nks, thread count and LDS bytes of the restatement; the two
+    LDS layouts follow the kernels' comments region by region; the bucket limits sit where the cases put them."""
+    cases = list(GC.CASES.values())
+    kern = lambda r: f"fast{r[0]}" if r[0] >= 0 else f"g{r[1]}"
+    rows = [list(map(int, r)) for r in plans([f"girf {c.N} {c.p} {c.Ny} {int(c.generic)}" for c in cases])]
+    for c, r in zip(cases, rows):
+        assert kern(r) == c.kernel, (c.name, r)
+        assert (kern(r), r[2], r[3], r[4]) == GC.plan(c.N, c.p, c.Ny, c.generic), (c.name, r)
+        assert r[3] == 64 * -(-c.N // 16) <= 128 and r[4] <= LDS_CU, c.name  # one wave per 16 equations, launch bound 128
+    got = {c.name: (kern(r), r[2]) for c, r in zip(cases, rows)}
+    assert {k for k, _ in got.values()} == {"g32", "g64", "g96", "fast0", "fast4", "fast8"}
+    assert [got[n] for n in ("n7_p15_bh1", "n8_p15", "n5_p21_bh1", "n15_p16", "n16_p15", "n12_p19_bh1", "n32_p9_bh7",
+                             "n20_p12_bh10")] == \
+        [("g32", 32), ("g64", 33), ("g64", 33), ("g64", 64), ("g96", 65), ("g96", 65), ("g96", 96), ("g96", 96)]
+    assert got["n20_p12_bh6_generic"] == ("g96", 84) and got["n20_p12_bh6"] == ("fast8", 84)
+    big = next(r for c, r in zip(cases, rows) if c.name == "n32_p9_bh7")
+    assert big[4] > 64 * 1024  # over the default dynamic-LDS limit: the launcher has to raise it
+    # layouts
+    gen = [(c, r) for c, r in zip(cases, rows) if r[0] < 0]
+    for (c, r), row in zip(gen, plans([f"girfg {c.N} {c.p} {r[2]}" for c, r in gen])):
+        _check_layout(row, GC.generic_regions(c.N, c.p, r[2]), {"X", "logsv", "ybuf", "nrm"})
+        assert int(row[0]) == r[4], c.name
+    fast = [(c, r) for c, r in zip(cases, rows) if r[0] >= 0]
+    for (c, r), row in zip(fast, plans([f"girff {c.N} {r[0]}" for c, r in fast])):
+        _check_layout(row, GC.fast_regions(c.N, r[0]), {"X", "logsv", "ybuf", "nrm"})
+        assert int(row[0]) == r[4], c.name
+    # the fast kernel serves N = 17..20 and Ny = 0..8 at p = 12 only; the refused shapes
+    q = [(N, p, Ny) for N in (16, 17, 20, 21) for p in (11, 12, 13) for Ny in (0, 1, 8, 9)]
+    for (N, p, Ny), r in zip(q, plans([f"girf {N} {p} {Ny} 0" for N, p, Ny in q])):
+        assert (int(r[0]) >= 0) == (17 <= N <= 20 and p == 12 and Ny <= 8), (N, p, Ny)
+    r385, rlds, r33 = (list(map(int, r)) for r in plans(["girf 32 11 0 0", "girf 2 127 0 0", "girf 2 126 0 0"]))
+    assert r385[1:3] == [0, 97]                               # KT = 385: no bucket
+    assert rlds[1:3] == [96, 65] and rlds[4] > LDS_CU         # 127 rows of the table: 166 KB
+    assert r33[4] <= LDS_CU
+
+
+def test_philox_words_bit_for_bit(plans):
+    """tests/philox.py against the library's own host function Rng::raw on 70 counters: idx = 0, 1, 2^31,
+    2^32 - 1, every block id the library uses, chains and sweeps up to 2^32 - 1, seeds below and above 2^32; and both
+    against the known answers of the Random123 distribution (kat_vectors, philox4x32-10)."""
+    import numpy as np
+    rng = np.random.default_rng(2011)
+    seeds = [0, 1, 1012023, 2**32 - 1, 2**32, (7 << 32) + 5, 2**64 - 1, 0xA4093822299F31D0]
+    q = [(idx, ch, sw, blk, sd) for idx in (0, 1, 2, 3, 2**31, 2**32 - 2, 2**32 - 1) for ch, sw, blk, sd in
+         [(0, 0, 9, seeds[2]), (1, 0, 10, seeds[5]), (2**32 - 1, 2**32 - 1, 1, seeds[6])]]
+    q += [(int(rng.integers(0, 2**32)), int(rng.integers(0, 2**32)), int(rng.integers(0, 2**32)), int(rng.integers(1, 11)),
+           seeds[i % len(seeds)]) for i in range(49)]
+    rows = plans([f"philox {i} {c} {s} {b} {sd & 0xFFFFFFFF} {sd >> 32}" for i, c, s, b, sd in q])
+    assert len(q) >= 64
+    for (i, c, s, b, sd), row in zip(q, rows):
+        want = [int(w) for w in philox.raw(sd, c, s, b, i >> 1)]
+        assert [int(t, 16) for t in row] == want, (i, c, s, b, hex(sd))
+    # array form == scalar form
+    idx = np.array([t[0] for t in q[21:]], np.uint64)
+    arr = philox.raw(seeds[2], 3, 0, 9, idx >> np.uint64(1))
+    for k, i in enumerate(idx):
+        assert [int(w[k]) for w in arr] == [int(w) for w in philox.raw(seeds[2], 3, 0, 9, int(i) >> 1)]
+    # Random123 known answers: counter and key all zero; all ones; the digits of pi
+    kat = [((0, 0, 0, 0), (0, 0), "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),
+           ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, "408f276d 41c83b0e a20bc7c6 6d5451fd"),
+           ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0),
+            "d16cfe09 94fdcceb 5001e420 24126ea1")]
+    lib = plans([f"philox {2 * c[0]} {c[1]} {c[2]} {c[3]} {k[0]} {k[1]}" for c, k, _ in kat if c[0] < 2**31])
+    for (c, k, want), row in zip([t for t in kat if t[0][0] < 2**31], lib):
+        assert " ".join(row) == want
+    for c, k, want in kat:
+        assert " ".join(f"{int(w):08x}" for w in philox.philox4x32_10(*c, *k)) == want
+    # u01 and the Box-Muller pair: (0, 1) open, 53 bits, even index cosine and odd index sine of one call
+    assert philox.u01(0, 0) == 2.0**-54 and philox.u01(0xFFFFFFFF, 0xFFFFFFFF) == 1 - 2.0**-54
+    assert philox.u01(0x800, 0) == 1.5 * 2.0**-53 and philox.u01(0x7FF, 0) == 2.0**-54
+    x, y, z, w = philox.raw(5, 1, 0, 9, 3)
+    u1, u2 = philox.u01(x, y), philox.u01(z, w)
+    n6, n7 = philox.normal(5, 1, 0, 9, 6), philox.normal(5, 1, 0, 9, 7)
+    assert abs(n6 * n6 + n7 * n7 + 2 * np.log(u1)) < 1e-14
+    assert abs(np.arctan2(n7, n6) % (2 * np.pi) - 2 * np.pi * u2) < 1e-14

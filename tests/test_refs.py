@@ -247,3 +247,51 @@ def test_fcst_chain_cases_cover_the_variants():
     assert all(v[n] == 0 for n in v if n.startswith("hy_"))
     assert {len(c[2]) for n, c in fcc.CHAIN_CASES.items() if n.startswith("hy_")} == {1, 4, 5}
     assert all(c[5] <= 17 and c[6] <= 3 for c in fcc.CHAIN_CASES.values())
+
+
+# ------------------------------------------------------------------ generalized impulse responses (tests/girf_cases.py)
+import girf_cases as gic  # noqa: E402
+
+
+@pytest.mark.parametrize("name", list(gic.CASES))
+def test_girf_oracle_vs_longdouble(name):
+    """oracle.ccmm_oracle_girf.girf_draw (dense companion, fp64) against refs.girf_ld (explicit state, longdouble)
+    on every shape case; measured 7.6e-16 at worst (n32_p9_bh7).  Every shadow-rate case has between 20% and 80% of
+    its simulated yield values below the ELB (measured 0.50-0.62), so the ring's max(y, ELB) and the output floor
+    both bind and both do not; the closest comparison with the bound is printed (smallest 1.7e-5, n19_p12_bh5)."""
+    c, d = gic.CASES[name], gic.inputs(name)
+    for m, ((ld, share, gap), orc) in enumerate(zip(gic.longdouble_reference(name), gic.oracle_reference(name))):
+        r = gic.spectral_radius(d["PAI"][..., m], c.N, c.p)
+        e = rel_err(orc, ld, 1.0)
+        print(f"girf {name} draw {m}: radius {r:.3f}, oracle vs longdouble {e:.2e}, share of yields below the ELB "
+              f"{share:.2f}, closest floor comparison {gap:.1e}")
+        assert r <= gic.RADIUS + 1e-9
+        assert e < BOUND, e
+        if c.model == "linear":
+            assert np.isnan(share) and gap == np.inf
+        else:
+            assert 0.2 <= share <= 0.8, share
+            assert gap >= 1e-7  # no floor decision within rounding of the bound
+
+
+def test_girf_cases_cover_the_kernel_edges():
+    """The shapes the case table is built for (tests/test_launch_plans.py holds the library's girf_plan to
+    girf_cases.plan): every kernel, the bucket limits, the wave tiles, the chunk masks."""
+    C = gic.CASES
+    for c in C.values():
+        assert gic.plan(c.N, c.p, c.Ny, c.generic)[0] == c.kernel, c.name
+        assert c.p > 12 or c.H > c.p, c.name  # the ring wraps
+    assert {c.kernel for c in C.values()} == {"g32", "g64", "g96", "fast0", "fast4", "fast8"}
+    assert {gic.nks_of(c.N, c.p, c.Ny) for c in C.values() if not c.kernel.startswith("fast")} >= {2, 32, 33, 64, 65, 96}
+    assert {c.N for c in C.values()} >= {1, 16, 17, 32} and {c.N for c in C.values() if c.kernel.startswith("fast")} == {17, 18, 19, 20}
+    assert {c.Ny for c in C.values() if c.kernel.startswith("fast")} >= {0, 1, 4, 5, 6, 8}
+    assert {c.nsim for c in C.values()} >= {1, 4, 5, 8, 9} and {c.p for c in C.values()} >= {1, 2, 12, 16}
+    assert any(c.H == 1 for c in C.values()) and any(c.cum is None for c in C.values())
+    assert {c.M for c in C.values()} == {1, 2, 3}
+    sub = C["n20_p12_bh4_sub"]
+    assert set(sub.actual) < set(range(sub.N)) - set(sub.yields)
+    a, b = gic.inputs("n20_p12_bh6"), gic.inputs("n20_p12_bh6_generic")
+    assert all(np.array_equal(a[k], b[k]) for k in ("PAI", "invA", "sqrtPHI", "SV0", "Xj", "z", "svz"))
+    assert {C[n].model for n in gic.PHILOX_CASES} == {"linear", "bh", "hybrid"} and any(C[n].M == 3 for n in gic.PHILOX_CASES)
+    assert {C[n].kernel[:1] for n in gic.PHILOX_CASES if C[n].model != "linear"} == {"g", "f"}
+    assert any(s >= 2**32 for s in gic.PHILOX_CASES.values())
