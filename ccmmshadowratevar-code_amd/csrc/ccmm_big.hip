@@ -464,16 +464,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_big(Dims d, const int* __restri
 //   L' x = y   left-looking: for block b the columns c of L below the block are contiguous,
 //              so lanes run over their rows and a DPP sum gives (L' x)_c
 //   X x        the K columns split in 8 slices x T in 64-row chunks, partial sums in LDS
-constexpr int kBSLd = 65;
-constexpr int kResSlices = 8;
-// staged twin (KP <= kStageMaxKP): the X'v and residual phases read the lag twin from LDS, 256 months
-// (plus the p - 1 presample rows their lags reach) at a time, instead of one L2 load per product
-constexpr int kStageMonths = 256;
-constexpr int kStageMaxKP = 320;
-__host__ __device__ inline int big_stage_rows(int p) { return kStageMonths + p; }
-__host__ inline size_t big_stage_lds_doubles(const Dims& d, const ColX& cx) {
-  return (size_t)cx.ncol * big_stage_rows(d.p) + (d.KP + 1) / 2;  // + the KP int offsets
-}
+// (kBSLd, kResSlices, the staging constants and the LDS layout: ccmm_big.h)
 __global__ __launch_bounds__(1024) void k_cta_solve_big(Dims d, const int* __restrict__ Tslot,
                                                         const double* __restrict__ iVb, XSel xs,
                                                         ChainState cs, const double* __restrict__ rdiag,
@@ -878,10 +869,6 @@ __global__ __launch_bounds__(1024) void k_cta_solve_big(Dims d, const int* __res
 }
 
 // ============================================================== host launchers
-size_t big_solve_lds_bytes(const Dims& d) {
-  return (size_t)(d.TP + 2 * d.KP + 64 * kBSLd + kResSlices * d.TP) * sizeof(double);
-}
-
 hipError_t big_launch_cta(hipStream_t st, const Dims& d, const int* Tslot, const int* slotIV,
                           const double* iVdiag, const double* iVb, XSel xs, ChainState cs,
                           const int4* groups, int ngroups, double* rdiag, RngArgs ra, double* Ubuf,
@@ -897,11 +884,11 @@ hipError_t big_launch_cta(hipStream_t st, const Dims& d, const int* Tslot, const
                        cskip);
   if (phase_mask & 4) {
     // the staged twin when the design fits kStageMaxKP and its LDS fits beside the rest
+    // (big_solve_plan)
     ColX cs_x = cx;
-    size_t lds = big_solve_lds_bytes(d);
-    const size_t lds_st = lds + big_stage_lds_doubles(d, cx) * sizeof(double);
-    if (!cx.pool || d.KP > kStageMaxKP || lds_st > 160 * 1024) cs_x.ncol = 0;
-    else lds = lds_st;
+    const BigSolvePlan pl = big_solve_plan(d, cx.pool != nullptr, cx.ncol);
+    if (!pl.staged) cs_x.ncol = 0;
+    const size_t lds = pl.lds;
     hipError_t e = hipFuncSetAttribute((const void*)k_cta_solve_big,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -16,15 +16,15 @@
 // The N x N matrices (115 KB at N = 120) no longer fit a CU's LDS several at a time, so
 // one of them lives in LDS (row-major, ld = 129 doubles) and the rest in per-chain global
 // scratch (L2 resident).  Workgroup primitives below: an LDS-staged Gram with 4 x 4
-// register tiles, a blocked Cholesky (32-wide panels: one wave factors the diagonal
+// register tiles, a blocked Cholesky (16-wide panels, kPB: one wave factors the diagonal
 // block with readlane broadcasts, all threads update), blocked triangular solves.
+// ccmm_bign.h holds kNL, kCB and every dynamic-LDS size with the kernel's layout beside it.
 #include "ccmm_bign.h"
 
 #include <cstdlib>
 
 namespace ccmm {
 
-constexpr int kNL = 129;   // LDS row stride of an N x N matrix (odd: spreads banks)
 constexpr int kPB = 16;    // Cholesky panel width (16: no spills at 1024 threads)
 constexpr int kGC = 32;    // Gram t-chunk
 
@@ -113,7 +113,7 @@ __device__ void wg_gram(double* G, const double* __restrict__ src, int sa, int s
 
 // ---------------------------------------------------------------- Cholesky (LDS)
 // In place on the lower triangle of S (n x n, ld kNL, n <= 128): blocked right-looking with
-// 32-wide panels.  Wave 0 factors the diagonal block (lane = row, readlane broadcasts);
+// 16-wide panels (kPB).  Wave 0 factors the diagonal block (lane = row, readlane broadcasts);
 // the panel below and the trailing update use every thread.  Upper triangle zeroed.
 // *bad set on a non-positive pivot (the pivot is then taken as 1).
 template <int NT>
@@ -493,8 +493,7 @@ __global__ __launch_bounds__(1024) void k_phi_big(Dims d, const int* __restrict_
 //     all:    trailing update;  Linv(block i, 0:p0) = -Dv_i T
 // The block products run on MFMA, one 16 x 16 block per wave.  Only the lower triangle is read
 // (the upper triangle of S may hold anything; diagonal blocks are masked).  Tb: LDS scratch,
-// kCB x 128 doubles.
-constexpr int kCB = 16;
+// kCB x 128 doubles (kCB = 16, ccmm_bign.h).
 
 template <int NT>
 __device__ void wg_chol_inv(double* S, int n, double* Tb, int* bad) {
@@ -930,24 +929,18 @@ __global__ __launch_bounds__(kSvNT) void k_sv_big(Dims d, const int* __restrict_
 }
 
 // ================================================================ host launchers
-size_t bign_sv_scratch(const Dims& d) {
-  return (size_t)d.N * d.N * (1 + 2 * (size_t)(d.TP + 1)) + (size_t)(d.TP + 1) * d.N;
-}
-
-int bign_astep_npad(const Dims& d) { return d.N <= 64 ? 64 : 128; }
-
 hipError_t bign_launch_astep(hipStream_t st, const Dims& d, const int* Tslot, ChainState cs, RngArgs ra,
                              double logy2offset, double* gbuf) {
   const int NPAD = bign_astep_npad(d);
   const int nt = NPAD / 64;
   const int ngr = (d.N - 1 + 3) / 4;
   hipLaunchKernelGGL(k_astep_gram, dim3(nt * (nt + 1) / 2, d.B * ngr), dim3(256), 0, st, d, Tslot, cs, gbuf, NPAD);
-  const size_t lds = (size_t)(128 * kNL + 128) * sizeof(double);
+  const size_t lds = bign_astep_lds();
   hipError_t e = hipFuncSetAttribute((const void*)k_astep_big, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_astep_big, dim3(d.N - 1, d.B), dim3(256), lds, st, d, Tslot, cs, ra, gbuf, NPAD);
-  const size_t lds2 = (size_t)d.N * d.N * sizeof(double);
+  const size_t lds2 = bign_astep_fin_lds(d.N);
   e = hipFuncSetAttribute((const void*)k_astep_fin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_astep_fin, dim3(d.B), dim3(256), lds2, st, d, Tslot, cs, logy2offset);
@@ -956,7 +949,7 @@ hipError_t bign_launch_astep(hipStream_t st, const Dims& d, const int* Tslot, Ch
 
 hipError_t bign_launch_phi(hipStream_t st, const Dims& d, const int* Tslot, int dPHI, const double* sPHI,
                            ChainState cs, double* scr) {
-  const size_t lds = (size_t)(128 * kNL) * sizeof(double);
+  const size_t lds = bign_phi_lds();
   hipError_t e = hipFuncSetAttribute((const void*)k_phi_big, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds);
   if (e != hipSuccess) return e;
@@ -966,7 +959,7 @@ hipError_t bign_launch_phi(hipStream_t st, const Dims& d, const int* Tslot, int 
 
 hipError_t bign_launch_sv(hipStream_t st, const Dims& d, const int* Tslot, const double* V0inv,
                           const double* V0invm, ChainState cs, RngArgs ra, double* scr) {
-  const size_t lds = (size_t)(d.N * kNL + kCB * 128 + 256) * sizeof(double);
+  const size_t lds = bign_sv_lds(d.N);
   hipError_t e = hipFuncSetAttribute((const void*)k_sv_big, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds);
   if (e != hipSuccess) return e;

@@ -38,7 +38,9 @@ void ccmm_chains::init(ccmm_ctx* c, const ccmm_chain_config& cf, int nX, int nY)
   else
     require(cf.K == cf.N * cf.p + 1 || cf.p == 0, "K must equal N*p+1");
   require(cf.K >= 1 && cf.K <= 1536, "K must be in [1, 1536]");
-  require(cf.T >= 2 && cf.B >= 1 && cf.ndata >= 1, "bad T/B/ndata");
+  // one month: the block calls of the large-N path only (k_sv_big then makes one forward step; a data slot
+  // still needs T >= 2, set_T); the small-path kernels are not run below two months
+  require((cf.T >= 2 || (cf.T == 1 && cf.N > kMaxNSmall)) && cf.B >= 1 && cf.ndata >= 1, "bad T/B/ndata");
   d.N = cf.N;
   d.p = cf.p;
   d.K = cf.K;

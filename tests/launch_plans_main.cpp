@@ -16,9 +16,15 @@
 //   girff N NY4                -> the same for k_girf_fast<12, 20, NY4>
 //   philox idx chain sweep block seedlo seedhi -> the four output words (hex) of Rng::raw(block, idx >> 1), the
 //                                 counter and key of the library's Philox4x32-10 normals and uniforms
+//   bign N TP                  -> bign_astep_npad, the LDS bytes of k_astep_big, k_astep_fin, k_phi_big and k_sv_big,
+//                                 bign_sv_scratch (doubles per chain)
+//   bsolve N p K KP TP twin ncol -> big_solve_plan: staged, LDS bytes; then big_solve_lds_bytes and
+//                                 big_stage_lds_doubles on their own
 #include <cstdio>
 #include <cstring>
 
+#include "ccmm_big.h"
+#include "ccmm_bign.h"
 #include "ccmm_elb.h"
 #include "ccmm_fcst.h"
 #include "ccmm_girf.h"
@@ -34,7 +40,7 @@ static void wave(const ElbWaveLds& l) {
 
 int main() {
   char cmd[16];
-  int a, b, c, d, e;
+  int a, b, c, d, e, f, g;
   unsigned u[6];
   while (std::scanf("%15s", cmd) == 1) {
     if (!std::strcmp(cmd, "cond") && std::scanf("%d %d %d", &a, &b, &c) == 3) {
@@ -81,6 +87,14 @@ int main() {
     } else if (!std::strcmp(cmd, "girff") && std::scanf("%d %d", &a, &b) == 2) {
       const GirfLds l = girf_fast_lds(a, kGirfFastP, kGirfFastN4, b);
       std::printf("%zu X:%zu logsv:%zu ybuf:%zu nrm:%zu\n", l.end, l.X, l.logsv, l.ybuf, l.nrm);
+    } else if (!std::strcmp(cmd, "bign") && std::scanf("%d %d", &a, &b) == 2) {
+      const Dims dm{a, 1, a + 1, round_up(a + 1, 64), b, 1, a};
+      std::printf("%d %zu %zu %zu %zu %zu\n", bign_astep_npad(dm), bign_astep_lds(), bign_astep_fin_lds(a), bign_phi_lds(),
+                  bign_sv_lds(a), bign_sv_scratch(dm));
+    } else if (!std::strcmp(cmd, "bsolve") && std::scanf("%d %d %d %d %d %d %d", &a, &b, &c, &d, &e, &f, &g) == 7) {
+      const Dims dm{a, b, c, d, e, 1, a};
+      const BigSolvePlan pl = big_solve_plan(dm, f != 0, g);
+      std::printf("%d %zu %zu %zu\n", (int)pl.staged, pl.lds, big_solve_lds_bytes(dm), big_stage_lds_doubles(dm, g));
     } else if (!std::strcmp(cmd, "philox") && std::scanf("%u %u %u %u %u %u", &u[0], &u[1], &u[2], &u[3], &u[4], &u[5]) == 6) {
       Rng rng{};
       rng.seed = ((uint64_t)u[5] << 32) | u[4];

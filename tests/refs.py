@@ -103,11 +103,44 @@ def sv_order(T, seps):
     return order + list(seps)
 
 
-def sv_dense_ld(D, b, Q, z):
+def chol_band_ld(P, bw):
+    """chol_ld for a matrix whose entries with |i - j| > bw are exactly zero: the factor has the same
+    band, so every dot product runs over the band only (the terms left out are products with exact
+    zeros).  Still one dense factorisation row by row; no block structure is used."""
+    n = P.shape[0]
+    L = np.zeros((n, n), LD)
+    for k in range(n):
+        lo, hi = max(0, k - bw), min(n, k + bw + 1)
+        d = P[k, k] - L[k, lo:k] @ L[k, lo:k]
+        assert d > 0, f"pivot {k} not positive"
+        L[k, k] = np.sqrt(d)
+        if k + 1 < hi:
+            L[k + 1:hi, k] = (P[k + 1:hi, k] - L[k + 1:hi, lo:k] @ L[k, lo:k]) / L[k, k]
+    return L
+
+
+def phi_iw_ld(eta, sPHI, Z):
+    """The inverse-Wishart draw of mcmcVAR.m:268-274 in longdouble: Lpost = chol(sPHI + eta' eta, 'lower'),
+    R = chol(Z Z') (upper), sqrtPHI_ = Lpost / R, PHI = sqrtPHI_ sqrtPHI_', sqrtPHI = chol(PHI, 'lower').
+    eta: T x N, Z: N x (T + dPHI).  Row r of Lpost / R solves R' x = Lpost(r, :)' (forward substitution on
+    the lower factor R' of Z Z').  Returns (sqrtPHI, PHI) rounded to float64."""
+    e = np.asarray(eta).astype(LD)
+    Zl = np.asarray(Z).astype(LD)
+    Lpost = chol_ld(np.asarray(sPHI).astype(LD) + e.T @ e)
+    Rt = chol_ld(Zl @ Zl.T)
+    Sq = np.stack([fwd_ld(Rt, Lpost[r]) for r in range(Lpost.shape[0])])
+    PHI = Sq @ Sq.T
+    return chol_ld(PHI).astype(np.float64), PHI.astype(np.float64)
+
+
+def sv_dense_ld(D, b, Q, z, order=None):
     """x = Pi' L^-T (L^-1 Pi b + Pi z) in longdouble, L the dense Cholesky factor of the whole
     (T+1)N-square block-tridiagonal precision (diagonal blocks D[t], off-diagonal blocks -Q)
-    permuted into the order Pi of ``sv_order``; z column t belongs to block t.  Returns x as
-    (T+1) x N float64.  Nothing here follows the block recursion of the partitioned sampler."""
+    permuted into the block order Pi; z column t belongs to block t.  order = None: the order of
+    ``sv_order`` (the partitioned sampler's declaration, N <= 32).  order = range(T + 1): time order, what
+    oracle.sv_draw_sequential declares for N > 32; the permuted matrix then has half bandwidth 2N - 1 and
+    the factorisation's dot products run over that band (chol_band_ld).  Returns x as (T+1) x N float64.
+    Nothing here follows the block recursion of either sampler."""
     T1, N = b.shape
     n = T1 * N
     P = np.zeros((n, n), LD)
@@ -117,11 +150,19 @@ def sv_dense_ld(D, b, Q, z):
         if t + 1 < T1:
             P[t * N:(t + 1) * N, (t + 1) * N:(t + 2) * N] = -Qd
             P[(t + 1) * N:(t + 2) * N, t * N:(t + 1) * N] = -Qd.T
-    from oracle.ccmm_oracle import sv_separators  # the declared separator positions only
-    perm = np.concatenate([np.arange(t * N, (t + 1) * N)
-                           for t in sv_order(T1 - 1, sv_separators(T1 - 1))])
+    if order is None:
+        from oracle.ccmm_oracle import sv_separators  # the declared separator positions only
+        blocks = sv_order(T1 - 1, sv_separators(T1 - 1))
+    else:
+        blocks = list(order)
+    perm = np.concatenate([np.arange(t * N, (t + 1) * N) for t in blocks])
     assert np.array_equal(np.sort(perm), np.arange(n))
-    L = chol_ld(P[np.ix_(perm, perm)])
+    Pp = P[np.ix_(perm, perm)]
+    if order is None:
+        L = chol_ld(Pp)
+    else:
+        i, j = np.nonzero(Pp)
+        L = chol_band_ld(Pp, int(np.max(np.abs(i - j))))
     bp = np.asarray(b).astype(LD).reshape(-1)[perm]
     zp = np.asarray(z).astype(LD).T.reshape(-1)[perm]
     xp = bwd_ld(L, fwd_ld(L, bp) + zp)

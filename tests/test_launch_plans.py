@@ -5,12 +5,14 @@ edge case, so that the edge asserts there (n65_lagbatch -> kb 10, long_w4 -> 4, 
 about the library, and against the layout comments of the kernels region by region.  The predictive-density
 launch (fcst_reg_path, fcst_chunk, fcst_variant, fcst_paths_lds_doubles) is checked on every case of
 tests/fcst_cases.py in the same way, and the GIRF launch (ccmm_girf.h girf_plan, girf_lds, girf_fast_lds) on every
-case of tests/girf_cases.py.  The same program prints the library's Philox4x32-10 words (Rng::raw), which pin
-tests/philox.py bit for bit."""
+case of tests/girf_cases.py.  The large-N path (ccmm_bign.h: the padded Gram dimension, the LDS sizes and the SV
+scratch for every N = 33..128; ccmm_big.h: big_solve_plan) is checked against tests/bign_cases.py.  The same program
+prints the library's Philox4x32-10 words (Rng::raw), which pin tests/philox.py bit for bit."""
 import subprocess
 
 import pytest
 
+import bign_cases as BC
 import elb_cases as EC
 import fcst_cases as FC
 import girf_cases as GC
@@ -215,6 +217,57 @@ def test_girf_plans_match_the_case_table(plans):
     assert r385[1:3] == [0, 97]                               # KT = 385: no bucket
     assert rlds[1:3] == [96, 65] and rlds[4] > LDS_CU         # 127 rows of the table: 166 KB
     assert r33[4] <= LDS_CU
+
+
+def test_bign_lds_and_scratch_for_every_n(plans):
+    """ccmm_bign.h on every N of the large path, at the smallest and a long TP: the padded Gram dimension, the
+    four dynamic-LDS sizes (each within one CU's LDS, each the sum of the regions of its layout comment) and the SV
+    scratch, whose first 3 N^2 doubles k_phi_big takes."""
+    q = [(N, TP) for N in range(33, 129) for TP in (32, 768)]
+    for (N, TP), row in zip(q, plans([f"bign {N} {TP}" for N, TP in q])):
+        npad, astep, fin, phi, sv, scratch = map(int, row)
+        assert npad == BC.astep_npad(N) and npad >= N and npad % 64 == 0, N
+        assert (astep, fin, phi, sv) == (BC.astep_lds(), N * N * 8, BC.phi_lds(), BC.sv_lds(N)), N
+        assert max(astep, fin, phi, sv) <= LDS_CU, N
+        # what the kernels index: rows up to N - 1 of a matrix with stride 129 (128 rows hold every N), wg_gram's
+        # staged chunk [32 x 129] and its 32 weights inside the same region, vec [128] after the A-step's matrix
+        assert astep // 8 - 128 == phi // 8 >= max((N - 1) * 129 + N, 32 * 129 + 32), N
+        assert scratch == BC.sv_scratch(N, TP) and scratch >= 3 * N * N, (N, TP)
+    assert [BC.astep_npad(N) for N in (33, 64, 65, 128)] == [64, 64, 128, 128]
+    assert BC.sv_lds(128) == 150528 and BC.astep_lds() == 133120  # the largest: 147 KB of 160
+
+
+def test_big_solve_plan_matches_the_restatement(plans):
+    """big_solve_plan (ccmm_big.h) on every sweep case of tests/bign_cases.py with and without a twin, and on the
+    S120 configuration: the branch, the LDS bytes, and the pair on the LDS boundary."""
+    cases = list(BC.SWEEPS) + [(120, 12, 750), (35, 2, 121)]
+    q = [(c, tw) for c in cases for tw in (1, 0)]
+    lines = []
+    for (N, p, T), tw in q:
+        K, KP, TP, ncol = BC.dims(N, p, T)
+        lines.append(f"bsolve {N} {p} {K} {KP} {TP} {tw} {ncol}")
+    got = {}
+    for ((N, p, T), tw), row in zip(q, plans(lines)):
+        K, KP, TP, ncol = BC.dims(N, p, T)
+        staged, lds, base, stage = map(int, row)
+        branch, want = BC.solve_plan(N, p, T, bool(tw))
+        assert (staged, lds) == (int(branch == "staged"), want), (N, p, T, tw)
+        assert (base, stage) == (BC.solve_lds(KP, TP), BC.stage_doubles(ncol, p, KP)), (N, p, T)
+        assert lds <= LDS_CU, (N, p, T)
+        got[(N, p, T), tw] = (branch, lds)
+    for c, branch in BC.SWEEPS.items():
+        assert got[c, 1][0] == branch and got[c, 0][0] == "none", c
+    assert {b for b in BC.SWEEPS.values()} == {"staged", "kp", "lds"}
+    # the LDS boundary: N = 58 stages with 1312 bytes to spare, N = 59 would need 744 bytes more than a CU has
+    assert got[(58, 1, 62), 1] == ("staged", LDS_CU - 1312)
+    K, KP, TP, ncol = BC.dims(59, 1, 62)
+    assert BC.solve_lds(KP, TP) + BC.stage_doubles(ncol, 1, KP) * 8 == LDS_CU + 744
+    assert got[(35, 9, 71), 1][0] == "staged" and BC.dims(35, 9, 71)[1] == 320  # the last staged KP
+    assert got[(120, 12, 750), 1][0] == "kp"
+    # a shape whose unstaged size alone exceeds a CU's LDS is not refused by the plan (the launcher's
+    # hipFuncSetAttribute returns the error): TP = 2048
+    r = list(map(int, plans(["bsolve 33 1 34 64 2048 1 35"])[0]))
+    assert r[0] == 0 and r[1] > LDS_CU
 
 
 def test_philox_words_bit_for_bit(plans):

@@ -295,3 +295,85 @@ def test_girf_cases_cover_the_kernel_edges():
     assert {C[n].model for n in gic.PHILOX_CASES} == {"linear", "bh", "hybrid"} and any(C[n].M == 3 for n in gic.PHILOX_CASES)
     assert {C[n].kernel[:1] for n in gic.PHILOX_CASES if C[n].model != "linear"} == {"g", "f"}
     assert any(s >= 2**32 for s in gic.PHILOX_CASES.values())
+
+
+# =============================================================================================
+# The large-N path (tests/bign_cases.py; tests/test_gpu_bign_edges.py holds the device to the longdouble
+# references on these cases).  Measured, fp64 oracle against longdouble in the units of the device tests: A-step
+# A 2.5e-12 (N = 128), invA 2.1e-12 at N = 33..36, 9e-12 at N = 63..65, 1.5e-11 at (66, 97), 1.0e-10 to 3.0e-10 at
+# N = 127, 128; PHI 1.3e-14; SV 5.0e-12 (N = 127, T = 4); the coefficient block of the sweep cases 2.2e-13.
+import bign_cases as bgc  # noqa: E402
+
+
+@pytest.mark.parametrize("N,T", bgc.ASTEP)
+def test_bign_astep_oracle_vs_longdouble(N, T):
+    """A within 1e-11 on every case.  invA within 1e-11 except on the cases of bign_cases.INVA_LOOSE (N >= 127, and
+    (66, 97) at 1.5e-11): forward substitution through that many rows puts the oracle itself at up to 3e-10 on entries
+    near the 1e-3 floor (not a fault of the inputs: rescaling the volatilities does not move it).  There the device
+    bound becomes ten times this figure (bign_cases.inva_bound) and the figure is only required to stay below 1e-9."""
+    for c, ((A, invA), (oA, oinvA), sd) in enumerate(bgc.astep_reference(N, T)):
+        eA, ei = rel_err(oA, A, sd), rel_err(oinvA, invA, 1e-3)
+        print(f"bign astep N={N} T={T} chain {c}: A {eA:.2e} invA {ei:.2e}")
+        assert eA < BOUND, eA
+        assert ei < (1e-9 if (N, T) in bgc.INVA_LOOSE else BOUND), ei
+    if (N, T) in bgc.INVA_LOOSE:
+        assert bgc.inva_bound(N, T, 1e-9) < 1e-8
+
+
+@pytest.mark.parametrize("N,T", [(N, T) for N, Ts in bgc.PHI.items() for T in Ts])
+def test_bign_phi_oracle_vs_longdouble(N, T):
+    for c, ((sq, PHI), (osq, oPHI)) in enumerate(bgc.phi_reference(N, T)):
+        e = max(rel_err(oPHI, PHI, np.abs(PHI).max()), rel_err(osq, sq, np.abs(sq).max()))
+        print(f"bign phi N={N} T={T} chain {c}: oracle vs longdouble {e:.2e}")
+        assert e < 1e-12, e  # the device bound of this block is 1e-11 (measured here: 1.3e-14 at worst)
+
+
+def _bign_sv_err(N, T, c):
+    h, h0, sh, _ = bgc.sv_oracle(N, T, c)
+    lh, lh0, lsh = bgc.sv_longdouble(N, T, c)
+    return max(rel_err(h, lh, 1.0), rel_err(sh, lsh, 1e-2), rel_err(h0, lh0, 1.0))
+
+
+@pytest.mark.parametrize("N,T", bgc.SV)
+def test_bign_sv_oracle_vs_longdouble(N, T):
+    """The time-ordered block recursion (oracle.sv_draw_sequential) against the dense time-ordered factorisation."""
+    e = _bign_sv_err(N, T, 0)
+    print(f"bign sv N={N} T={T}: oracle vs dense longdouble {e:.2e}")
+    assert e < BOUND, e
+
+
+def test_bign_sv_multi_oracle_vs_longdouble():
+    N, T, B = bgc.SV_MULTI
+    for c in range(B):
+        e = _bign_sv_err(N, T, c)
+        print(f"bign sv N={N} T={T} chain {c}: oracle vs dense longdouble {e:.2e}")
+        assert e < BOUND, e
+
+
+def test_sv_dense_ld_time_order_is_the_band_of_the_dense_factor():
+    """chol_band_ld against chol_ld on a time-ordered system (the terms it leaves out are exact zeros), and the
+    default order of sv_dense_ld unchanged by the new argument."""
+    import refs
+    y, hprev, sqrtPHI, h0mean, h0vcvsqrt, u, z = sc.sv_chain(5, 6, 0)
+    kai = sc.O.ksc_indicators(y, hprev, u)
+    D, b, Q = sc.O.sv_precision(y - sc.O.KSC_MEAN[kai - 1], 1.0 / sc.O.KSC_VAR[kai - 1], sqrtPHI, h0mean, h0vcvsqrt)
+    x = refs.sv_dense_ld(D, b, Q, z, order=range(7))
+    np.testing.assert_allclose(x, sc.O.sv_draw_sequential(D, b, Q, z), rtol=0, atol=1e-12)
+    P = np.zeros((35, 35), refs.LD)
+    for t in range(7):
+        P[5 * t:5 * t + 5, 5 * t:5 * t + 5] = D[t]
+        if t < 6:
+            P[5 * t:5 * t + 5, 5 * t + 5:5 * t + 10] = -Q
+            P[5 * t + 5:5 * t + 10, 5 * t:5 * t + 5] = -Q.T
+    assert float(np.max(np.abs(refs.chol_band_ld(P, 9) - refs.chol_ld(P)))) < 1e-17
+    np.testing.assert_array_equal(refs.sv_dense_ld(D, b, Q, z), refs.sv_dense_ld(D, b, Q, z, order=None))
+
+
+@pytest.mark.parametrize("N,p,T", list(bgc.SWEEPS))
+def test_bign_sweep_cta_oracle_vs_longdouble(N, p, T):
+    """The coefficient block of every sweep case on the pre-sweep state of chain 0."""
+    _, orc, sd, ld = bgc.sweep_reference(N, p, T)[0]
+    e = rel_err(orc, ld, sd)
+    print(f"bign sweep N={N} p={p} T={T}: coefficient block, oracle vs longdouble {e:.2e}")
+    assert e < BOUND, e
+    assert bgc.solve_plan(N, p, T)[0] == bgc.SWEEPS[N, p, T]
