@@ -30,6 +30,7 @@ MODEL_SHADOWRATE = 3  # mcmcVARshadowrate.m: shadow-rate design for all equation
 RNG_PAI, RNG_A, RNG_SVU, RNG_SVZ, RNG_PHI, RNG_ELB, RNG_FCST, RNG_PS = 1, 2, 3, 4, 5, 6, 7, 8
 RNG_PSALT = 9  # randn(nmiss,1) of the alternate draw (mcmcVARshadowrateBlockHybrid.m:471-475)
 STATUS_PS = 128  # missing-data / alternate draw: precision not positive definite (invalid draws)
+STATUS_NONSTATIONARY = 256  # check_stationarity: max_attempts redraws exhausted (invalid draws)
 # treatment of the ELB months (ccmm_chains_set_elb_treatment); _PAIR: MISSING by the unfused kernel pair
 ELB_TREAT_SHADOW, ELB_TREAT_MISSING, ELB_TREAT_MISSING_PAIR = 0, 1, 2
 CCMM_WARN_MVNCDF = 3
@@ -156,6 +157,11 @@ _SIGS = {
                                         _dp, _dp, _dp, _dp, _dp]),
     "ccmm_chains_summaries_floor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, _u8p, _u8p, C.c_double, _dp,
                                               C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ccmm_max_var_root_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
+    "ccmm_max_var_root": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
+    "ccmm_chains_max_var_roots": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
+    "ccmm_chains_set_stationarity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ccmm_chains_get_stationarity": (C.c_int, [C.c_void_p, _i64p]),
     "ccmm_chains_get_ps": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
     "ccmm_chains_get_ps_mean": (C.c_int, [C.c_void_p, _dp]),
     "ccmm_chains_keep_missingrate": (C.c_int, [C.c_void_p, C.c_int]),
@@ -260,6 +266,29 @@ def _ptr(a, ct=_dp):
     if a is None:
         return None
     return a.ctypes.data_as(ct)
+
+
+def _pai_batch(PAI_all, N, p):
+    """PAI_all M x K x N (or K x N) -> (M, K, C-contiguous M x N x K: each matrix K x N column-major)."""
+    P = np.asarray(PAI_all, dtype=np.float64)
+    if P.ndim == 2:
+        P = P[None]
+    M, K, Nn = P.shape
+    if Nn != N or K < N * p + 1:
+        raise ValueError(f"PAI_all must be M x K x N with K >= 1 + N p; got {P.shape} for N={N}, p={p}")
+    return M, K, np.ascontiguousarray(np.swapaxes(P, 1, 2))
+
+
+def max_var_root_host(PAI_all, N, p, return_info=False):
+    """ccmm_max_var_root_host: max |eig| of the companion matrix of each PAI (M x K x N), by the library's
+    fp64 Hessenberg + double-shift QR on the CPU (at most 16 threads; no GPU needed).  info per matrix: 0
+    converged, 1 non-finite coefficients (NaN root), 2 iteration cap."""
+    M, K, P = _pai_batch(PAI_all, N, p)
+    out = np.zeros(M)
+    info = np.zeros(M, dtype=np.int32)
+    _check(load_library().ccmm_max_var_root_host(M, int(N), int(p), K, _ptr(P), _ptr(out), _ptr(info, _ip)),
+           "ccmm_max_var_root_host")
+    return (out, info) if return_info else out
 
 
 def psrf(X):
@@ -549,6 +578,16 @@ class Context:
                "ccmm_draw_summaries")
         return out
 
+    def max_var_root(self, PAI_all, N, p, return_info=False):
+        """ccmm_max_var_root: max |eig| of the companion of each PAI (M x K x N) on the device for
+        N p <= 256 (bit-identical to max_var_root_host), on the CPU otherwise.  info as max_var_root_host."""
+        M, K, P = _pai_batch(PAI_all, N, p)
+        out = np.zeros(M)
+        info = np.zeros(M, dtype=np.int32)
+        _check(self.lib.ccmm_max_var_root(self.handle, M, int(N), int(p), K, _ptr(P), _ptr(out), _ptr(info, _ip)),
+               "ccmm_max_var_root")
+        return (out, info) if return_info else out
+
     def girf(self, PAI, invA, sqrtPHI, SV0, Xjumpoff, H, nsim, shock11, *, bh=False, actual=None,
              ndxYields=None, elb=0.25, cumcode=None, np_=12, z=None, svz=None, seed=1012023,
              hybrid=False, ndxShadow=None, p=None):
@@ -683,7 +722,8 @@ class Chains:
                "k_sv_mix", "k_sv_part", "k_phi_gen", "k_phi", "k_store", "k_gram_chol",
                "k_elb_prep", "k_elb_cond", "k_elb_gibbs", "k_elb_rebuild", "k_gram_chol_lag",
                "k_cta_solve_lag", "k_fcst", "k_gram_big", "k_chol_big", "k_cta_solve_big",
-               "k_astep_big", "k_sv_big", "k_phi_big", "k_ps_chol", "k_ps_prop")
+               "k_astep_big", "k_sv_big", "k_phi_big", "k_ps_chol", "k_ps_prop", "k_eig_maxroot",
+               "k_stat_select")
 
     def __init__(self, ctx: Context, *, N, p, T, B, ndata=1, model=MODEL_LINEAR, crn=False,
                  store_capacity=0, logy2offset=1e-3, seed=1012023, dPHI=None, Ns=0, elbTmax=0,
@@ -833,6 +873,31 @@ class Chains:
         assert a.size == self.B
         _check(self.lib.ccmm_chains_set_rng_ids(self.handle, a.ctypes.data_as(C.POINTER(C.c_uint32))),
                "ccmm_chains_set_rng_ids")
+
+    def set_stationarity(self, enable=True, max_attempts=1000):
+        """check_stationarity (ccmm_chains_set_stationarity): redraw a chain's PAI while its companion's
+        maximum root is >= 1, at most max_attempts times per sweep (then STATUS_NONSTATIONARY).  Philox mode
+        only."""
+        _check(self.lib.ccmm_chains_set_stationarity(self.handle, int(bool(enable)), int(max_attempts)),
+               "ccmm_chains_set_stationarity")
+
+    def get_stationarity(self):
+        """Coefficient blocks drawn again per chain since set_state (B int64)."""
+        out = np.zeros(self.B, dtype=np.int64)
+        _check(self.lib.ccmm_chains_get_stationarity(self.handle, out.ctypes.data_as(_i64p)),
+               "ccmm_chains_get_stationarity")
+        return out
+
+    def max_var_roots(self, slot=0, return_info=False):
+        """ccmm_chains_max_var_roots: maximum VAR root of every stored PAI draw of the chains bound to
+        ``slot``, read in place on the device; stored x C values, draw slowest, chain fastest (the order of
+        ``max_var_roots(np.moveaxis(PAI_all, 3, 1).reshape(-1, K, N), N, p)``).  The store is kept."""
+        st = self.stored()
+        out = np.zeros(st * self.B)  # room for every chain; the call returns the slot's chain count
+        info = np.zeros(st * self.B, dtype=np.int32)
+        nC = _check(self.lib.ccmm_chains_max_var_roots(self.handle, int(slot), _ptr(out), _ptr(info, _ip)),
+                    "ccmm_chains_max_var_roots")
+        return (out[:st * nC], info[:st * nC]) if return_info else out[:st * nC]
 
     def get_status(self):
         st = np.zeros(self.B, dtype=np.int32)

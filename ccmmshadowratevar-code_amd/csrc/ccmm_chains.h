@@ -1,13 +1,15 @@
 // A device-resident chain set (ccmm_chains of include/ccmm.h): every member, block by block, and the
 // methods' declarations.  The bodies are in the unit of their block: ccmm_chains.hip (set-up, data, state,
 // exports, profile), ccmm_chains_sweep.hip (the Gibbs blocks of a sweep), ccmm_chains_elb.hip (ELB step,
-// PS branch, treatment), ccmm_chains_fcst.hip (predictive density, summaries).
+// PS branch, treatment), ccmm_chains_fcst.hip (predictive density, summaries), ccmm_chains_eig.hip (maximum VAR
+// roots, check_stationarity).
 #pragma once
 #include "ccmm_host.h"
 #include "ccmm_sweep.h"
 #include "ccmm_elb.h"
 #include "ccmm_lag.h"
 #include "ccmm_big.h"
+#include "ccmm_eig.h"
 
 // hidden: the methods are called across the host units only, never from outside the library, so the calls
 // bind at link time as they did inside one unit (no procedure-linkage stub, no lazy lookup at a first call)
@@ -168,6 +170,17 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   DBuf<double> paiPrev, zHost;
   int64_t qr_count = 0;
 
+  // ---------------------------------------------------------------- maximum VAR root / stationarity
+  // ccmm_chains_eig.hip: roots of the stored draws (ccmm_chains_max_var_roots) and check_stationarity
+  // (mcmcVAR.m:221-232): after the coefficient block of a sweep the roots of the B new PAI, and while a
+  // chain's root is >= 1 the block again for the whole set with the attempt's normals (RngArgs::attempt),
+  // the accepted chains' PAI, E and status put back from a snapshot (k_stat_select)
+  bool stat_on = false;
+  int stat_max = 1000;
+  std::vector<int64_t> statRedraws;
+  DBuf<double> eigRoot, eigScr, statPAI, statE;
+  DBuf<int> eigInfo, statAcc, statStatus;
+
   // ---------------------------------------------------------------- profiling
   bool profiling = false;
   struct Ev {
@@ -290,4 +303,13 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   void summaries(int source, int sl, const uint8_t* rows, const uint8_t* cumcode, const uint8_t* flo, double fl,
                  const double* realized, int nq, const double* pct, double* mean, double* median, double* quant,
                  double* sdev, double* crps);
+
+  // ================================================================ ccmm_chains_eig.hip
+  void run_stationarity(const ccmm::RngArgs& ra);
 };
+
+// max |eig| of M companions whose PAI are on the device (src: ccmm_eig.h EigSrc), results on the host: the
+// device kernel for N p <= kEigMaxN, the host twin for larger orders and for the matrices with info = 2.
+// root / info / scr: the caller's device buffers, grown as needed.  info may be null.  (ccmm_chains_eig.hip)
+void max_var_root_device_src(ccmm_ctx* ctx, int M, int N, int p, const ccmm::EigSrc& src, DBuf<double>& root,
+                             DBuf<int>& finfo, DBuf<double>& scr, double* maxroot, int* info);

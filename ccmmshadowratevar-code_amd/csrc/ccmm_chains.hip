@@ -13,7 +13,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_resid",       "k_cta_weights",   "k_cta_solve", "k_astep",    "k_sv_mix",   "k_sv_part",       "k_phi_gen",
     "k_phi",         "k_store",         "k_gram_chol", "k_elb_prep", "k_elb_cond", "k_elb_gibbs",     "k_elb_rebuild",
     "k_gram_chol_lag", "k_cta_solve_lag", "k_fcst",    "k_gram_big", "k_chol_big", "k_cta_solve_big", "k_astep_big",
-    "k_sv_big",      "k_phi_big",       "k_ps_chol",   "k_ps_prop"};
+    "k_sv_big",      "k_phi_big",       "k_ps_chol",   "k_ps_prop",
+    "k_eig_maxroot", "k_stat_select"};
 
 void ccmm_chains::init(ccmm_ctx* c, const ccmm_chain_config& cf, int nX, int nY) {
   ctx = c;
@@ -704,6 +705,7 @@ int ccmm_chains_set_state(ccmm_chains* ch, const double* PAI, const double* A,
     HIPCHECK(hipMemset(ch->status.p, 0, ch->cfg.B * sizeof(int)));
     if (ch->psCount.p) HIPCHECK(hipMemset(ch->psCount.p, 0, 2 * (size_t)ch->cfg.B * sizeof(int)));
     if (ch->have_fcst) ch->reset_fcst();
+    ch->statRedraws.assign(ch->cfg.B, 0);
     ch->resid_valid = false;
     ch->have_state = true;
     return 0;

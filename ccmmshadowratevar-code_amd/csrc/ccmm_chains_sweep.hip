@@ -372,6 +372,7 @@ void ccmm_chains::sweep_once(const double* dcrn, int64_t stride, bool store) {
   snapshot_pai();
   run_cta(ra);
   cta_fallback(ra);
+  if (stat_on) run_stationarity(ra);  // check_stationarity: redraw PAI while its companion's root is >= 1
   run_astep(ra);
   run_sv(ra);
   // block hybrid, N <= 32: the PHI block on the auxiliary stream beside the ELB step (the ELB kernels

@@ -103,6 +103,8 @@ enum KernelId {
   KID_PHIBIG,
   KID_PSCHOL,
   KID_PSPROP,
+  KID_EIG,
+  KID_STATSEL,
   KID_COUNT
 };
 extern const char* const kKernelNames[KID_COUNT];  // ccmm_chains.hip

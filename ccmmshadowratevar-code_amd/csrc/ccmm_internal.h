@@ -35,8 +35,9 @@ inline hipError_t launch_k(K k, dim3 grid, dim3 block, size_t lds, bool raise, h
 #endif
 
 // ---------------------------------------------------------------- RNG
-// Philox4x32-10 (Salmon et al. 2011), counter = (pair index, chain, sweep, block),
-// key = 64-bit seed.  Two doubles per call; normals by Box-Muller.
+// Philox4x32-10 (Salmon et al. 2011), counter = (pair index, chain, sweep, block | attempt << 8),
+// key = 64-bit seed.  Two doubles per call; normals by Box-Muller.  attempt is 0 except in the redraws of
+// check_stationarity (ccmm_chains_set_stationarity), so every other counter is (.., block).
 constexpr int kRngBlocks = 10;  // CCMM_RNG_* ids 1..9
 
 struct u32x4 {
@@ -72,9 +73,10 @@ struct Rng {
   uint64_t seed;
   uint32_t chain, sweep;
   int64_t off[kRngBlocks];  // CRN block offsets (indexed by CCMM_RNG_* id)
+  uint32_t attempt = 0;     // check_stationarity redraw (< 2^24), 0: the sweep's ordinary draw
 
   __host__ __device__ inline u32x4 raw(int block, uint32_t pair) const {
-    return philox4x32_10(u32x4{pair, chain, sweep, (uint32_t)block}, (uint32_t)seed,
+    return philox4x32_10(u32x4{pair, chain, sweep, (uint32_t)block | attempt << 8}, (uint32_t)seed,
                          (uint32_t)(seed >> 32));
   }
   __device__ inline double uniform(int block, uint32_t idx) const {
@@ -159,6 +161,7 @@ struct RngArgs {
   uint32_t sweep;
   int64_t off[kRngBlocks];
   const uint32_t* ids;     // Philox stream id of chain c (counter word 1), nullptr: c
+  uint32_t attempt = 0;    // check_stationarity redraw, 0: the sweep's ordinary draw
 
   __device__ inline Rng make(int c) const {
     Rng r;
@@ -166,6 +169,7 @@ struct RngArgs {
     r.seed = seed;
     r.chain = ids ? ids[c] : (uint32_t)c;
     r.sweep = sweep;
+    r.attempt = attempt;
 #pragma unroll
     for (int i = 0; i < kRngBlocks; ++i) r.off[i] = off[i];
     return r;

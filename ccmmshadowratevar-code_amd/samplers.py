@@ -31,17 +31,17 @@ def context(device: int = 0) -> _abi.Context:
 def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATSprior,
             ndxYIELDS=None, ELBbound=0.25, check_stationarity=0, yrealized=None, fcstNdraws=None,
             fcstNhorizons=None, rndStream=1012023, doprogress=False, *, nchains=1, device=0,
-            burnin=None):
+            burnin=None, stats=None):
     """mcmcVAR.m (linear BVAR-SV, CTA + A + SV + PHI blocks), nargout == 4.
+
+    check_stationarity=1 (:221-232): PAI is drawn again while its companion's maximum root is >= 1
+    (Chains.set_stationarity); ``stats`` (a dict, optional) then receives stationarityRedraws (per chain).
 
     rndStream: integer seed of the Philox stream (the MATLAB RandStream object
     has no device equivalent; chains c = 0..nchains-1 use counter word `chain`).
     Returns PAI_all (M x K x N), PHI_all (M x N(N+1)/2), invA_all (M x N x N),
     sqrtht_all (M x T x N), each with a trailing chain axis when nchains > 1.
     """
-    if check_stationarity:
-        raise NotImplementedError("check_stationarity=1 (mcmcVAR.m:221-232) is not supported; "
-                                  "the reference drivers all pass 0")
     doPredictiveDensity = bool(fcstNdraws)
     if doPredictiveDensity:
         if fcstNdraws % MCMCdraws != 0:  # mcmcVAR.m:97-99
@@ -55,6 +55,8 @@ def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATS
     ch = _abi.Chains(ctx, N=m.N, p=m.p, T=m.T, B=B, ndata=1, crn=False,
                      store_capacity=MCMCdraws, seed=int(rndStream))
     ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
+    if check_stationarity:
+        ch.set_stationarity(True)
     st = initial_state(m, B)
     ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
     if doPredictiveDensity:
@@ -62,6 +64,7 @@ def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATS
                                           yrealized, fcstNdraws, fcstNhorizons, doprogress)
     else:
         _run_chain_set(ch, burn, MCMCdraws, doprogress)
+    _stationarity_stats(ch, check_stationarity, stats)
     out = ch.get_draws()
     ch.close()
     res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"]]
@@ -98,6 +101,17 @@ def _run_with_predictive_density(ch, m, burn, MCMCdraws, ndxYIELDS, ELBbound, yr
     scores = [fc["scores"][:, :, k, :].reshape(fcstNdraws, B, order="F") for k in range(4)]
     return [fYd, fYd.mean(axis=2), fYcd, fYcd.mean(axis=2), fYs, fYs.mean(axis=2),
             fc["yhatsum"] / MCMCdraws] + scores
+
+
+def _stationarity_stats(ch, check_stationarity, stats):
+    """After a run with check_stationarity: a chain that exhausted its redraws (STATUS_NONSTATIONARY) is an
+    error, as every other failure bit; stats["stationarityRedraws"] = the redraws per chain."""
+    if not check_stationarity:
+        return
+    if np.any(ch.get_status() & _abi.STATUS_NONSTATIONARY):
+        raise RuntimeError("check_stationarity: a chain found no stationary PAI within the redraw cap")
+    if stats is not None:
+        stats["stationarityRedraws"] = ch.get_stationarity()
 
 
 def _refuse_gibbs_on_nan(where):
@@ -145,10 +159,9 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     the absent VARTVPSVprecisionsamplerNaN, first accepted, else the Gibbs draw).
     elb_ps=False keeps the Gibbs branch at every sweep.  ``stats`` (a dict, optional)
     receives countELBaccept / countELBacceptBurnin / stackAccept (:303-305, 453-460).
+    check_stationarity=1 (:333-347): PAI is drawn again while its companion's maximum root is >= 1;
+    ``stats`` then also receives stationarityRedraws (per chain).
     Indices are 0-based; actualrateBlock is a bool vector of length N."""
-    if check_stationarity:
-        raise NotImplementedError("check_stationarity=1 is not supported; the reference drivers "
-                                  "all pass 0")
     if not doELBsampling and not doELBsampleAlternate:
         _refuse_gibbs_on_nan("mcmcVARshadowrateBlockHybrid.m:494")
     missing = not doELBsampling
@@ -182,6 +195,8 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
         ch.set_elb_ps(Nproposals, max(1, -(-burn // 2)))  # m >= MCMCburnin * .5 (:435)
     if missing or alternate:
         ch.set_elb_treatment(missing=missing, alternate=alternate)  # :481-499 / :470-475
+    if check_stationarity:
+        ch.set_stationarity(True)                                   # :333-347
     st = initial_state(m, B)
     ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
     if doPredictiveDensity:
@@ -195,6 +210,7 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     _run_chain_set(ch, burn, MCMCdraws, doprogress)
     if doPredictiveDensity:
         fc = ch.get_fcst(paths=True)
+    _stationarity_stats(ch, check_stationarity, stats)
     if stats is not None and elb_ps:
         ps = ch.get_ps()
         stats.update(countELBaccept=ps["countAccept"], countELBacceptBurnin=ps["countAcceptBurnin"],
@@ -232,10 +248,8 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
     treatment of :442-459, the sweep's one unconstrained draw, which is also the data, and
     shadowrate_all is NaN), fcstYdraws, fcstYhat, fcstYcensorDraws, fcstYcensorHat, fcstShadowrateDraws, fcstShadowrateHat,
     fcstYhatRB, fcstLogscoreDraws, fcstLogscoreXdraws, fcstLogscoreIdraws, stackAccept
-    (:630-700).  Indices 0-based."""
-    if check_stationarity:
-        raise NotImplementedError("check_stationarity=1 is not supported; the reference drivers "
-                                  "all pass 0")
+    (:630-700).  check_stationarity=1: PAI is drawn again while its companion's maximum root is >= 1;
+    ``stats`` then also receives stationarityRedraws (per chain).  Indices 0-based."""
     if doPAIactual:
         raise NotImplementedError("doPAIactual = true (CTA on the actual data, :322-324) is not built")
     missing = not doELBsampling
@@ -272,9 +286,12 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
         other[bm.ndxO] = True
         ch.set_fcst_censor(other)                             # :539-546
         ch.set_fcst_slot(0, np.asarray(yrealized, float).reshape(N, -1, order="F")[:, 0])
+    if check_stationarity:
+        ch.set_stationarity(True)
     st = initial_state(m, B)
     ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
     _run_chain_set(ch, burn, MCMCdraws, doprogress)
+    _stationarity_stats(ch, check_stationarity, stats)
     stack = np.zeros((MCMCdraws, B), np.int32)
     if Nproposals:
         ps = ch.get_ps()
@@ -559,9 +576,12 @@ SET_QUANTILES = np.array([.5, 2.5, 5, _normcdf(-1) * 100, 25, 75, (1 - _normcdf(
                           99.5])
 
 
-def max_var_roots(PAI_all, N, p, threads=16):
+def max_var_roots(PAI_all, N, p, threads=16, device=None):
     """max(abs(eig(comp))) of every draw's companion matrix (goVARshadowrateBlockHybrid.m:
-    384-392), PAI_all M x K x N; host LAPACK (dgeev) over a thread pool."""
+    384-392), PAI_all M x K x N.  device=None: numpy's eigvals (LAPACK dgeev) over a thread pool, the
+    comparison path; device=d: the library's kernel on HIP device d (Context.max_var_root)."""
+    if device is not None:
+        return context(int(device)).max_var_root(PAI_all, N, p)
     from concurrent.futures import ThreadPoolExecutor
     M = PAI_all.shape[0]
     Np = N * p
@@ -703,7 +723,8 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                                      chunk=50, max_retries=2, keep_draws=False, progress=False,
                                      Nproposals=1000, elb_ps=True, postprocess=False, cumcode=None,
                                      setQuantiles=None, maxlambda=False, model="blockhybrid",
-                                     engine="python", doELBsampling=True):
+                                     engine="python", doELBsampling=True, check_stationarity=0,
+                                     engine_roots="device"):
     """The quasi-real-time OOS run of goVARshadowrateBlockHybrid.m:126-517 for the block-
     hybrid shadow-rate VAR, as ONE device-resident chain set per rank: every vintage
     thisT in Tjumpoffs (default: ydates > 2008-12, :127) is a data slot of the set with
@@ -736,7 +757,14 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     cumulated forms fcstYcum* (cumsum over horizons for ``cumcode``), fcstShadowYmedian /
     fcstShadowYquantiles, PAImedian / PAIquantiles, the score draws fcstYmvlogscore*Draws;
     setQuantiles default goVARshadowrateBlockHybrid.m:141.  maxlambda=True adds
-    drawsMaxVARroot (max |eig| of each draw's companion matrix, :382-392, host LAPACK).
+    drawsMaxVARroot (max |eig| of each draw's companion matrix, :382-392): engine_roots="device" takes
+    them from the stored draws in HBM (Chains.max_var_roots, no PAI download), engine_roots="host" downloads
+    PAI and calls numpy's eigvals over 16 threads (the comparison path).
+
+    check_stationarity=1 ("Truncate nonstationary draws?", the switch at the top of the reference drivers)
+    is passed to every vintage's chains (Chains.set_stationarity); a chain that exhausts its redraws fails
+    its vintage, which is re-run like any flagged one.  The hybrid model warns and ignores it
+    (mcmcVARhybridGibbs.m:22-24).  Python engine only.
 
     model="hybrid" runs goVARhybrid.m instead (goVARhybrid_batch): mcmcVARhybridGibbs per
     vintage (K = N p + 1 + Ns p, PS proposals at every sweep, :458), modellabel ELBhybrid; the
@@ -809,6 +837,16 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     elbdummy = data0[:, ndxSHADOWRATE] <= ELBbound                      # ELBdummy, :131
     if hybrid and maxlambda:
         raise ValueError("goVARhybrid.m computes no max VAR roots (:383-430 commented out)")
+    if engine_roots not in ("device", "host"):
+        raise ValueError(f"engine_roots must be 'device' or 'host', not {engine_roots!r}")
+    if check_stationarity and engine == "native":
+        raise ValueError("check_stationarity runs on the Python engine (engine='python'): "
+                         "ccmm_batch_config carries no field for it")
+    if check_stationarity and hybrid:
+        import warnings
+        warnings.warn("no stationarity check for hybrid model")          # mcmcVARhybridGibbs.m:22-24
+        check_stationarity = 0
+    dev_roots = maxlambda and engine_roots == "device"
     K = N * p + 1 + (ndxSHADOWRATE.size * p if hybrid else 0)
     costs = [dm.unit_cost(t - p, K, N, n_cens=dm.censored_months(data0, ndxSHADOWRATE, ELBbound, startELB, t)) * C
              for t in Tjumpoffs]
@@ -850,6 +888,8 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
             ch.set_elb_ps(Nproposals, 1 if hybrid else max(1, -(-burn // 2)))
             if is_sr:
                 ch.keep_missingrate(True)                  # mcmcVARshadowrate.m:435, 498
+        if check_stationarity:
+            ch.set_stationarity(True)
         B = ch.B
         done = 0
         while done < burn:
@@ -867,12 +907,16 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         elbTmax = ch.elbTmax
         shadow = np.empty((MCMCdraws, Ns, elbTmax, B)) if elbTmax else None
         miss = np.empty((MCMCdraws, Ns, elbTmax, B)) if (missing and elbTmax) else None
-        PAIdraws = np.empty((MCMCdraws, K, N, B)) if (keep_draws or maxlambda) else None
+        PAIdraws = np.empty((MCMCdraws, K, N, B)) if (keep_draws or (maxlambda and not dev_roots)) else None
+        roots = np.empty((MCMCdraws, B)) if dev_roots else None   # kept draw x chain
         post = {}
         done = 0
         while done < MCMCdraws:
             n = min(chunk, MCMCdraws - done)
             ch.sweep(n, store=True)
+            if dev_roots and not dev:  # the chunk's stored draws, before get_draws empties the store
+                for k in range(len(vidx)):
+                    roots[done:done + n, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(n, C)
             if not dev:
                 fc = ch.get_fcst()
                 if miss is not None:
@@ -920,6 +964,9 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                 if progress and (k % 8 == 7 or k == len(vidx) - 1):
                     print(f"[rank {rank}] device summaries {k + 1}/{len(vidx)} vintages "
                           f"({time.perf_counter() - t1:.1f} s)", flush=True)
+            if dev_roots:
+                for k in range(len(vidx)):
+                    roots[:, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(MCMCdraws, C)
             fc = ch.get_fcst()
             scores[:] = fc["scores"]
             fYsum[:] = fc["fYsum"]
@@ -1035,8 +1082,10 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                 P = PAIdraws[..., cs]
                 if keep_draws:
                     r["PAI_all"] = P
-                if maxlambda:
+                if maxlambda and not dev_roots:
                     r["drawsMaxVARroot"] = max_var_roots(np.moveaxis(P, 3, 1).reshape(-1, K, N), N, p)
+            if dev_roots:
+                r["drawsMaxVARroot"] = roots[:, cs].ravel()                 # draw slowest, chain fastest
             res[mine[i]] = r
             if progress and (k % 4 == 3 or k == len(vidx) - 1):
                 print(f"[rank {rank}] results {k + 1}/{len(vidx)} vintages ({time.perf_counter() - t1:.1f} s)",

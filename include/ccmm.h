@@ -505,6 +505,42 @@ int ccmm_chains_summaries_floor(ccmm_chains* ch, int source, int slot, const uin
                                 const double* pct, double* mean, double* median, double* quantiles, double* stdev,
                                 double* crps);
 
+/* ------------------------------------------------------------ maximum VAR root
+ * max(abs(eig(comp))) of the N p x N p companion matrix of each of M coefficient matrices
+ * (goVARshadowrateBlockHybrid.m:382-392 drawsMaxVARroot; mcmcVAR.m:221-232 check_stationarity): rows
+ * 1..N p of PAI (K x N column-major, K >= 1 + N p, M matrices K N doubles apart) transposed on top, the
+ * shifted identity below.  fp64 Householder reduction to Hessenberg form and implicit double-shift QR,
+ * eigenvalues only.  maxroot: M doubles.  info: M ints, 0 converged, 1 a NaN or Inf among the n x N
+ * coefficients (maxroot = NaN, nothing iterated), 2 the cap of 30 n QR iterations was reached (never seen;
+ * maxroot = the largest modulus deflated by then); may be NULL. */
+/* On the CPU (at most 16 threads); needs no context and no GPU. */
+int ccmm_max_var_root_host(int M, int N, int p, int K, const double* PAI, double* maxroot, int* info);
+/* Host PAI; on the device for N p <= 256 (one wave per matrix, bit-identical to the host function),
+ * on the CPU for larger N p and for any matrix the device returned info = 2 for. */
+int ccmm_max_var_root(ccmm_ctx* ctx, int M, int N, int p, int K, const double* PAI, double* maxroot, int* info);
+/* The stored PAI draws of the chains bound to data slot `slot` (contiguous chain indices), read in place
+ * on the device: maxroot[m * C + c] for stored draw m (slowest) and the slot's c-th chain (fastest),
+ * stored x C values; info likewise or NULL.  Returns C (> 0), or a negative error code.  The draw store is
+ * left as it is. */
+int ccmm_chains_max_var_roots(ccmm_chains* ch, int slot, double* maxroot, int* info);
+
+/* check_stationarity (mcmcVAR.m:221-232, mcmcVARshadowrateBlockHybrid.m:333-347): with enable != 0 every
+ * sweep computes the maximum VAR root of each chain's new PAI after the coefficient block and, while a chain's
+ * root is >= 1 (or not finite), draws its coefficient block again from the rejected PAI with fresh normals; the
+ * chains already accepted keep their draw.  One host synchronisation per sweep and one more per redraw round
+ * (few open chains go to the host function, many to the kernel: same bits).  The reference loops without
+ * bound; here a chain still non-stationary after max_attempts redraws (<= 0: the default, 1000; at most 2^24 - 1)
+ * keeps its last draw and gets CCMM_STATUS_NONSTATIONARY.
+ * Normals: attempt 0 is the sweep's ordinary draw (every counter as without the option).  Redraw a >= 1 of a
+ * chain takes its CCMM_RNG_PAI normals from the Philox counter (pair index, chain id, sweep,
+ * CCMM_RNG_PAI | a << 8): word 3 of attempt 0 is the block id alone (< 256), so the streams are disjoint and a
+ * function of (seed, chain id, sweep, a) only.  Philox mode only: CCMM_ERR_ARG on a CRN chain set (its layout
+ * holds one randn(K, N) block per sweep).  Off (the default) launches nothing and changes nothing. */
+#define CCMM_STATUS_NONSTATIONARY 256  /* check_stationarity: max_attempts redraws exhausted (invalid draws) */
+int ccmm_chains_set_stationarity(ccmm_chains* ch, int enable, int max_attempts);
+/* redraws: B values, the coefficient blocks drawn again per chain since ccmm_chains_set_state. */
+int ccmm_chains_get_stationarity(ccmm_chains* ch, int64_t* redraws /* B */);
+
 /* ------------------------------------------------------------ batch run (the vintage loop)
  * ccmm_run_batch replaces the parfor over vintages of goVARshadowrateBlockHybrid.m:258-517
  * (goVARhybrid.m:258 for the hybrid model, goVAR.m:242 for the linear one) for the vintages

@@ -66,7 +66,8 @@ def main():
         "workload": f"configs[3]: goVARshadowrateBlockHybrid full OOS run, {V} vintages x {args.chains} chain(s), "
                     f"{args.draws} burn-in + {args.draws} kept sweeps each, fcstNdraws = {10 * args.draws}, "
                     "48 horizons, ELB 0.25 (Gibbs for m < 500, then 1000 PS proposals with Gibbs fallback), "
-                    "per-vintage post-processing on the device, max VAR root on the host, QRT .mat written",
+                    "per-vintage post-processing and max VAR root of every stored draw on the device, "
+                    "QRT .mat written",
         "wall_s": {"total": round(time.perf_counter() - t_all, 2), "batch": round(t_batch, 2),
                    "setup": round(st["setup_s"], 2), "sampling_and_postprocess": round(st["run_s"], 2),
                    "save_mat": round(t_save, 2)},
