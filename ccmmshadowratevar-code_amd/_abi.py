@@ -160,6 +160,9 @@ _SIGS = {
     "ccmm_max_var_root_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_max_var_root": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_chains_max_var_roots": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
+    "ccmm_diagnostics_host": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, _dp, _dp]),
+    "ccmm_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
+    "ccmm_chains_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
     "ccmm_chains_set_stationarity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ccmm_chains_get_stationarity": (C.c_int, [C.c_void_p, _i64p]),
     "ccmm_chains_get_ps": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
@@ -289,6 +292,45 @@ def max_var_root_host(PAI_all, N, p, return_info=False):
     _check(load_library().ccmm_max_var_root_host(M, int(N), int(p), K, _ptr(P), _ptr(out), _ptr(info, _ip)),
            "ccmm_max_var_root_host")
     return (out, info) if return_info else out
+
+
+DIAG_NAMES = ("pmean", "pstd", "nse", "rne", "nse1", "rne1", "nse2", "rne2", "nse3", "rne3", "psrf")
+
+
+def _diag_dict(out):
+    """11 x ... statistics -> dict under DIAG_NAMES plus the inefficiency factors if1..3 = 1 / rne1..3
+    (ineff, Diagnostics.m:129-132)."""
+    d = {k: out[i] for i, k in enumerate(DIAG_NAMES)}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for j in (1, 2, 3):
+            d[f"if{j}"] = 1.0 / d[f"rne{j}"]
+    return d
+
+
+def _diag_draws(draws):
+    d = np.asarray(draws, dtype=np.float64)
+    if d.ndim == 1:
+        d = d[:, None]
+    if d.ndim != 2:
+        raise ValueError(f"draws must be M x S; got {d.shape}")
+    return d
+
+
+def diagnostics_host(draws, *, transposed=False):
+    """ccmm_diagnostics_host: momentg, ineff and the one-chain psrf of Diagnostics.m for every column of
+    ``draws`` (M x S), on the CPU (at most 16 threads; no GPU needed).  Returns a dict of S-vectors: pmean, pstd,
+    nse, rne, nse1, rne1, nse2, rne2, nse3, rne3, psrf and if1..if3 = 1 / rne1..3.  transposed=True hands the
+    library the draws with the series fastest (ld_series = 1): the same bits."""
+    d = _diag_draws(draws)
+    M, S = d.shape
+    out = np.zeros((len(DIAG_NAMES), S))
+    if transposed:
+        a, ld_draw, ld_series = np.ascontiguousarray(d), S, 1
+    else:
+        a, ld_draw, ld_series = np.asfortranarray(d), 1, M
+    rc = load_library().ccmm_diagnostics_host(M, S, ld_draw, ld_series, _ptr(a), _ptr(out))
+    _check(rc, "ccmm_diagnostics_host")
+    return _diag_dict(out)
 
 
 def psrf(X):
@@ -588,6 +630,15 @@ class Context:
                "ccmm_max_var_root")
         return (out, info) if return_info else out
 
+    def diagnostics(self, draws):
+        """ccmm_diagnostics: as diagnostics_host, by the kernel k_diag_series on the device (the same bits)."""
+        d = np.asfortranarray(_diag_draws(draws))
+        M, S = d.shape
+        out = np.zeros((len(DIAG_NAMES), S))
+        rc = self.lib.ccmm_diagnostics(self.handle, M, S, _ptr(d), _ptr(out))
+        _check(rc, "ccmm_diagnostics")
+        return _diag_dict(out)
+
     def girf(self, PAI, invA, sqrtPHI, SV0, Xjumpoff, H, nsim, shock11, *, bh=False, actual=None,
              ndxYields=None, elb=0.25, cumcode=None, np_=12, z=None, svz=None, seed=1012023,
              hybrid=False, ndxShadow=None, p=None):
@@ -723,7 +774,7 @@ class Chains:
                "k_elb_prep", "k_elb_cond", "k_elb_gibbs", "k_elb_rebuild", "k_gram_chol_lag",
                "k_cta_solve_lag", "k_fcst", "k_gram_big", "k_chol_big", "k_cta_solve_big",
                "k_astep_big", "k_sv_big", "k_phi_big", "k_ps_chol", "k_ps_prop", "k_eig_maxroot",
-               "k_stat_select")
+               "k_stat_select", "k_diag_series")
 
     def __init__(self, ctx: Context, *, N, p, T, B, ndata=1, model=MODEL_LINEAR, crn=False,
                  store_capacity=0, logy2offset=1e-3, seed=1012023, dPHI=None, Ns=0, elbTmax=0,
@@ -740,6 +791,7 @@ class Chains:
             raise RuntimeError(f"ccmm_chains_create failed: {last_error()}")
         self.handle = h
         self.N, self.p, self.K, self.T, self.B = N, p, K, T, B
+        self._slotT, self._slotElbT = {}, {}  # per data slot, for the shapes of diagnostics()
         for k, v in (options or {}).items():
             self.set_option(k, v)
 
@@ -806,6 +858,7 @@ class Chains:
                                            _ptr(_f(iVdiag)), _ptr(_f(iVb)), _ptr(_f(sPHI)),
                                            _ptr(_f(h0mean)), _ptr(_f(h0vcvsqrt)))
         _check(rc, "ccmm_chains_set_data")
+        self._slotT[int(slot)] = Y.shape[0]
 
     def set_slots(self, slots):
         s = np.ascontiguousarray(slots, dtype=np.int32)
@@ -898,6 +951,38 @@ class Chains:
         nC = _check(self.lib.ccmm_chains_max_var_roots(self.handle, int(slot), _ptr(out), _ptr(info, _ip)),
                     "ccmm_chains_max_var_roots")
         return (out[:st * nC], info[:st * nC]) if return_info else out[:st * nC]
+
+    DIAG_SOURCES = {"PAI": 0, "PHI": 1, "invA": 2, "sqrtht": 3, "shadowrate": 4}
+
+    def diagnostics(self, source, slot=0):
+        """ccmm_chains_diagnostics: Diagnostics.m per series of the stored draws of the chains bound to ``slot``,
+        read in place on the device (the store is kept; it needs at least 100 stored draws).  source 0 / "PAI"
+        -> arrays K x N x C, 1 / "PHI" -> N(N+1)/2 x C, 2 / "invA" -> N x N x C, 3 / "sqrtht" -> T x N x C with
+        the slot's T, 4 / "shadowrate" -> Ns x elbT x C (NaN outside the slot's sNaN).  Returns the dict of
+        diagnostics_host."""
+        src = self.DIAG_SOURCES.get(source, source)
+        N, K, T = self.N, self.K, self.T
+        if src not in (0, 1, 2, 3, 4):
+            raise ValueError(f"source must be one of {list(self.DIAG_SOURCES)} or 0..4; got {source!r}")
+        if src == 4 and not self.Ns * self.elbTmax:
+            raise ValueError("source 4 (shadowrate) needs a shadow-rate model")
+        S = (K * N, N * (N + 1) // 2, N * N, T * N, self.Ns * self.elbTmax)[src]
+        buf = np.zeros(len(DIAG_NAMES) * self.B * S)  # room for every chain; the call returns the slot's count
+        rc = self.lib.ccmm_chains_diagnostics(self.handle, int(src), int(slot), _ptr(buf))
+        nC = _check(rc, "ccmm_chains_diagnostics")
+        out = buf[:len(DIAG_NAMES) * nC * S].reshape(len(DIAG_NAMES), nC, S)
+        if src == 0:
+            out = out.reshape(-1, nC, N, K).transpose(0, 3, 2, 1)
+        elif src == 2:
+            out = out.reshape(-1, nC, N, N).transpose(0, 3, 2, 1)
+        elif src == 3:
+            out = out.reshape(-1, nC, N, T).transpose(0, 3, 2, 1)[:, :self._slotT.get(int(slot), T)]
+        elif src == 4:
+            eT = self._slotElbT.get(int(slot), self.elbTmax)
+            out = out.reshape(-1, nC, self.elbTmax, self.Ns).transpose(0, 3, 2, 1)[:, :, :eT]
+        else:
+            out = out.transpose(0, 2, 1)
+        return _diag_dict(np.ascontiguousarray(out))
 
     def get_status(self):
         st = np.zeros(self.B, dtype=np.int32)
@@ -1014,6 +1099,7 @@ class Chains:
         _check(self.lib.ccmm_chains_set_elb_slot(self.handle, int(slot), int(elbT0),
                                                  m.ctypes.data_as(_u8p) if m.size else None),
                "ccmm_chains_set_elb_slot")
+        self._slotElbT[int(slot)] = m.shape[1] if m.ndim == 2 and m.size else 0
 
     def set_elb_ps(self, nproposals=1000, ps_from_m=1):
         """Acceptance-sampling branch (mcmcVARshadowrateBlockHybrid.m:435-466) from sweep

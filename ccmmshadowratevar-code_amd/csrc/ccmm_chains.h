@@ -2,7 +2,7 @@
 // methods' declarations.  The bodies are in the unit of their block: ccmm_chains.hip (set-up, data, state,
 // exports, profile), ccmm_chains_sweep.hip (the Gibbs blocks of a sweep), ccmm_chains_elb.hip (ELB step,
 // PS branch, treatment), ccmm_chains_fcst.hip (predictive density, summaries), ccmm_chains_eig.hip (maximum VAR
-// roots, check_stationarity).
+// roots, check_stationarity), ccmm_chains_diag.hip (Compute_diagnostics of the stored draws).
 #pragma once
 #include "ccmm_host.h"
 #include "ccmm_sweep.h"
@@ -180,6 +180,13 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   std::vector<int64_t> statRedraws;
   DBuf<double> eigRoot, eigScr, statPAI, statE;
   DBuf<int> eigInfo, statAcc, statStatus;
+
+  // ---------------------------------------------------------------- diagnostics
+  // ccmm_chains_diag.hip: the 11 statistics of every stored series of one slot, the mask of the entries that
+  // are computed (sqrtht rows of the slot's T) and the per-chain entry counts (shadow rates within elbT)
+  DBuf<double> diagOut;
+  DBuf<uint8_t> diagMask;
+  DBuf<int> diagCnt;
 
   // ---------------------------------------------------------------- profiling
   bool profiling = false;

@@ -1,13 +1,19 @@
 // Convergence diagnostics of the OOS drivers: psrf (DiagnosticsShadowrate.m:34-128, the same
 // function as Diagnostics.m:28) and shadowratePSRF (goVARshadowrateBlockHybrid.m:322-325,
 // goVARhybrid.m:322-323, goVARshadowrate.m:332-333).  Host code: the inputs are the kept shadow-rate
-// draws the batch loop already holds on the host, a few MB per vintage.
+// draws the batch loop already holds on the host, a few MB per vintage.  ccmm_diagnostics_host is the host twin of
+// the device diagnostics (Diagnostics.m momentg / ineff / psrf per series; core in ccmm_diagk.h).
+#include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <exception>
+#include <thread>
 #include <limits>
 #include <string>
 #include <vector>
 
 #include "../../include/ccmm.h"
+#include "ccmm_diagk.h"
 #include "ccmm_err.h"
 
 namespace {
@@ -125,4 +131,36 @@ extern "C" int ccmm_shadowrate_psrf(int M, int Ns, int elbT, int ldT, int C, con
 extern "C" int ccmm_shadowrate_psrf_chains(int M, int Ns, int elbT, int ldT, int C, const double* draws,
                                            const uint8_t* mask, double* out) {
   return shadow_psrf(M, Ns, elbT, ldT, C, draws, mask, out, true, "ccmm_shadowrate_psrf_chains");
+}
+
+// Host twin of k_diag_series (ccmm_diagk.hip): the same core, one series at a time, on at most 16 threads.
+extern "C" int ccmm_diagnostics_host(int M, int S, long long ld_draw, long long ld_series, const double* draws,
+                                     double* out) {
+  if (S < 0 || (S > 0 && (!draws || !out))) {
+    ccmm::set_last_error("ccmm_diagnostics_host: S >= 0, draws and out required");
+    return CCMM_ERR_ARG;
+  }
+  if (M < ccmm::kDiagNG) {  // Diagnostics.m:185-187
+    ccmm::set_last_error("momentg: needs a larger number of ndraws");
+    return CCMM_ERR_ARG;
+  }
+  try {
+    std::atomic<int> next{0};
+    auto work = [&] {
+      double cn[ccmm::kDiagNG], st[ccmm::kDiagNStat];
+      for (int s; (s = next++) < S;) {
+        ccmm::diag_series(draws + (long long)s * ld_series, ld_draw, M, [&](int ig) -> double& { return cn[ig]; }, st);
+        for (int k = 0; k < ccmm::kDiagNStat; ++k) out[(size_t)k * S + s] = st[k];
+      }
+    };
+    const unsigned nth = std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u);
+    std::vector<std::thread> th;
+    for (unsigned i = 1; i < std::min<unsigned>(nth, (unsigned)std::max(S, 1) / 64 + 1); ++i) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+  } catch (const std::exception& e) {  // thread start
+    ccmm::set_last_error(e.what());
+    return CCMM_ERR_HIP;
+  }
+  return CCMM_OK;
 }

@@ -105,6 +105,7 @@ enum KernelId {
   KID_PSPROP,
   KID_EIG,
   KID_STATSEL,
+  KID_DIAG,
   KID_COUNT
 };
 extern const char* const kKernelNames[KID_COUNT];  // ccmm_chains.hip

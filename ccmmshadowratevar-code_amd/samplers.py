@@ -31,8 +31,12 @@ def context(device: int = 0) -> _abi.Context:
 def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATSprior,
             ndxYIELDS=None, ELBbound=0.25, check_stationarity=0, yrealized=None, fcstNdraws=None,
             fcstNhorizons=None, rndStream=1012023, doprogress=False, *, nchains=1, device=0,
-            burnin=None, stats=None):
+            burnin=None, stats=None, Compute_diagnostics=False):
     """mcmcVAR.m (linear BVAR-SV, CTA + A + SV + PHI blocks), nargout == 4.
+
+    Compute_diagnostics=True (the switch of goVAR.m beside check_stationarity): ``stats`` (a dict) receives
+    "diagnostics", the block means of Diagnostics.m:3-25 of the stored draws, taken on the device before the
+    draws are downloaded (keys of ``Diagnostics``, averaged over the chains).
 
     check_stationarity=1 (:221-232): PAI is drawn again while its companion's maximum root is >= 1
     (Chains.set_stationarity); ``stats`` (a dict, optional) then receives stationarityRedraws (per chain).
@@ -42,6 +46,7 @@ def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATS
     Returns PAI_all (M x K x N), PHI_all (M x N(N+1)/2), invA_all (M x N x N),
     sqrtht_all (M x T x N), each with a trailing chain axis when nchains > 1.
     """
+    _check_diag_draws(Compute_diagnostics, MCMCdraws)
     doPredictiveDensity = bool(fcstNdraws)
     if doPredictiveDensity:
         if fcstNdraws % MCMCdraws != 0:  # mcmcVAR.m:97-99
@@ -65,6 +70,8 @@ def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATS
     else:
         _run_chain_set(ch, burn, MCMCdraws, doprogress)
     _stationarity_stats(ch, check_stationarity, stats)
+    if Compute_diagnostics and stats is not None:
+        stats["diagnostics"] = _chain_diagnostics(ch, 0)
     out = ch.get_draws()
     ch.close()
     res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"]]
@@ -112,6 +119,67 @@ def _stationarity_stats(ch, check_stationarity, stats):
         raise RuntimeError("check_stationarity: a chain found no stationary PAI within the redraw cap")
     if stats is not None:
         stats["stationarityRedraws"] = ch.get_stationarity()
+
+
+DIAG_KEYS = ("SVpsrf", "SVif", "PAIpsrf", "PAIif", "invApsrf", "invAif", "PHIpsrf", "PHIif")
+
+
+def _check_diag_draws(Compute_diagnostics, MCMCdraws):
+    if Compute_diagnostics and MCMCdraws < 100:
+        raise ValueError("momentg: needs a larger number of ndraws")     # Diagnostics.m:185-187
+
+
+def _diag_block(d, axes):
+    """mean(psrf(.)) and mean(ineff(.)) of Diagnostics.m:6-25 over the axes of one block's series (a plain
+    mean: NaN propagates as in MATLAB); the remaining axes come first, the three tapers last."""
+    return np.mean(d["psrf"], axis=axes), np.stack([np.mean(d[f"if{j}"], axis=axes) for j in (1, 2, 3)], axis=-1)
+
+
+def _chain_diagnostics(ch, slot):
+    """Diagnostics.m:3-25 of the stored draws of the chains of one data slot, on the device
+    (Chains.diagnostics, sources 0-3), per chain and then averaged over the slot's chains (the convention of
+    shadowratePSRF).  The invA block is the strict lower triangle, which for a unit-lower-triangular invA is the
+    filter of :19.  Returns SVpsrf (N), SVif (N x 3), and psrf (scalar) / if (3) of PAI, invA and PHI."""
+    N = ch.N
+    out = {}
+    ps, fi = _diag_block(ch.diagnostics(3, slot), 0)                     # T x N x C -> N x C, N x C x 3
+    out["SVpsrf"], out["SVif"] = ps.mean(axis=-1), fi.mean(axis=1)
+    ps, fi = _diag_block(ch.diagnostics(0, slot), (0, 1))                # K x N x C -> C, C x 3
+    out["PAIpsrf"], out["PAIif"] = ps.mean(), fi.mean(axis=0)
+    d = ch.diagnostics(2, slot)
+    low = np.tril(np.ones((N, N), bool), -1)
+    ps, fi = _diag_block({k: v[low] for k, v in d.items()}, 0)
+    out["invApsrf"], out["invAif"] = ps.mean(), fi.mean(axis=0)
+    ps, fi = _diag_block(ch.diagnostics(1, slot), 0)
+    out["PHIpsrf"], out["PHIif"] = ps.mean(), fi.mean(axis=0)
+    return out
+
+
+def Diagnostics(sqrtht, invA, PAI, PHI, N, K, M, *, device=0):
+    """Diagnostics.m (Compute_diagnostics of the reference drivers, goVARshadowrateBlockHybrid.m:313-316) on the
+    device: sqrtht M x T x N, invA M x N x N, PAI M x K x N, PHI M x N(N+1)/2, the reference's signature and
+    layouts.  Instead of printing it returns a dict: SVpsrf (N) and SVif (N x 3; 4 / 8 / 15 % tapers) per
+    volatility equation (:3-10), PAIpsrf / PAIif (3) (:13-15), invApsrf / invAif over the columns whose first draw
+    is neither 0 nor 1 (:18-21), PHIpsrf / PHIif (:24-25).  Each is the plain mean over the block's series."""
+    ctx = context(device)
+    sqrtht, invA, PAI, PHI = (np.asarray(a, float) for a in (sqrtht, invA, PAI, PHI))
+    if sqrtht.shape[0] != M or sqrtht.shape[2] != N or PAI.shape != (M, K, N) or invA.shape != (M, N, N):
+        raise ValueError("Diagnostics: sqrtht M x T x N, invA M x N x N, PAI M x K x N, PHI M x N(N+1)/2")
+    _check_diag_draws(True, M)
+    out = {}
+    T = sqrtht.shape[1]
+    ps, fi = _diag_block({k: v.reshape(T, N, order="F") for k, v in
+                          ctx.diagnostics(sqrtht.reshape(M, T * N, order="F")).items()}, 0)
+    out["SVpsrf"], out["SVif"] = ps, fi
+    out["PAIpsrf"], out["PAIif"] = _diag_block(ctx.diagnostics(PAI.reshape(M, K * N, order="F")), 0)
+    temp = invA.reshape(M, N * N, order="F")
+    temp2 = temp[:, ~((temp[0] == 1) | (temp[0] == 0))]                  # :19
+    if temp2.shape[1]:
+        out["invApsrf"], out["invAif"] = _diag_block(ctx.diagnostics(temp2), 0)
+    else:
+        out["invApsrf"], out["invAif"] = np.nan, np.full(3, np.nan)
+    out["PHIpsrf"], out["PHIif"] = _diag_block(ctx.diagnostics(PHI.reshape(M, -1, order="F")), 0)
+    return out
 
 
 def _refuse_gibbs_on_nan(where):
@@ -506,7 +574,7 @@ def _rank_device(dist, device):
 def goVAR_batch(data0, ydates0, Tjumpoffs, p, np_, MCMCdraws, fcstNdraws, fcstNhorizons,
                 minnesotaPriorMean, ndxYIELDS, ELBbound=0.25, doRATSprior=True, *, nchains=1,
                 rndStream=1012023, dist=None, device=None, burnin=None, run_vintage=None,
-                ndxSHADOWRATE=None):
+                ndxSHADOWRATE=None, Compute_diagnostics=False):
     """The quasi-real-time OOS loop of goVAR.m:242 / goVARshadowrateBlockHybrid.m:258-517
     for the linear sampler: every vintage thisT in Tjumpoffs runs mcmcVAR with its
     predictive density; vintages are sharded over ranks longest-processing-time first
@@ -520,8 +588,14 @@ def goVAR_batch(data0, ydates0, Tjumpoffs, p, np_, MCMCdraws, fcstNdraws, fcstNh
     (goVAR.m:262-267; ``realized_values``).  ``run_vintage(thisT, yrealized, seed)``
     replaces the mcmcVAR call (tests use it to drive the sharding on CPU).  ``device``
     defaults to the rank's LOCAL_RANK under a process group.  Returns a dict on every rank.
+
+    Compute_diagnostics=True (goVAR.m's switch, Diagnostics.m) adds diagSVpsrf (N x V), diagSVif (N x 3 x V),
+    diagPAIpsrf / diagInvApsrf / diagPHIpsrf (V) and diagPAIif / diagInvAif / diagPHIif (3 x V): the block means of
+    Diagnostics.m:3-25 of each vintage's kept draws, taken on the device and averaged over the chains (NaN for a
+    vintage run by ``run_vintage``).  MCMCdraws < 100 raises momentg's error before anything runs.
     """
     from . import distributed as dm
+    _check_diag_draws(Compute_diagnostics, MCMCdraws)
     data0 = np.asarray(data0, float)
     Nobs, N = data0.shape
     K = N * p + 1
@@ -537,24 +611,39 @@ def goVAR_batch(data0, ydates0, Tjumpoffs, p, np_, MCMCdraws, fcstNdraws, fcstNh
         thisT = Tjumpoffs[v]
         yreal = realized_values(data0, thisT, H, ndxSHADOWRATE, ELBbound)
         seed = int(rndStream) + 7919 * v  # per-vintage stream (initRandStreams analogue)
+        stats = {}
         if run_vintage is not None:
             ls, lsELB, lsX, lsI, fYhat = run_vintage(thisT, yreal, seed)
         else:
             out = mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean,
                           doRATSprior, ndxYIELDS=ndxYIELDS, ELBbound=ELBbound, yrealized=yreal,
                           fcstNdraws=fcstNdraws, fcstNhorizons=H, rndStream=seed,
-                          nchains=nchains, device=device, burnin=burnin)
+                          nchains=nchains, device=device, burnin=burnin, stats=stats,
+                          Compute_diagnostics=Compute_diagnostics)
             fYhat = out[5]
             ls, lsELB, lsX, lsI = out[11], out[12], out[13], out[14]
             if nchains > 1:
                 fYhat = fYhat.mean(axis=-1)
         summ = [_logmeanexp(np.ravel(a)) for a in (ls, lsELB, lsX, lsI)]
         local[v] = np.concatenate([np.array(summ), np.ravel(fYhat, order="F")])
+        if Compute_diagnostics:
+            dg = stats.get("diagnostics")
+            tail = (np.full(4 * N + 12, np.nan) if dg is None else
+                    np.concatenate([np.ravel(dg[k], order="F") for k in DIAG_KEYS]))
+            local[v] = np.concatenate([local[v], tail])
     allv = dm.gather_summaries(dist, local, None)
     S = np.stack([allv[v] for v in range(len(Tjumpoffs))], axis=1)
-    return dict(fcstYmvlogscore=S[0], fcstYmvlogscoreELB=S[1], fcstYmvlogscoreX=S[2],
-                fcstYmvlogscoreI=S[3], fcstYhat=S[4:].reshape(N, H, -1, order="F"),
-                assignment=dm.lpt_assign(costs, size))
+    res = dict(fcstYmvlogscore=S[0], fcstYmvlogscoreELB=S[1], fcstYmvlogscoreX=S[2],
+               fcstYmvlogscoreI=S[3], fcstYhat=S[4:4 + N * H].reshape(N, H, -1, order="F"),
+               assignment=dm.lpt_assign(costs, size))
+    if Compute_diagnostics:
+        D = S[4 + N * H:]
+        o = 0
+        for k, shp in zip(DIAG_KEYS, ((N,), (N, 3), (), (3,), (), (3,), (), (3,))):
+            n = int(np.prod(shp, dtype=int))
+            res["diag" + k[0].upper() + k[1:]] = D[o:o + n].reshape(shp + (D.shape[1],), order="F")
+            o += n
+    return res
 
 
 # ---------------------------------------------------------------------------------------
@@ -724,7 +813,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                                      Nproposals=1000, elb_ps=True, postprocess=False, cumcode=None,
                                      setQuantiles=None, maxlambda=False, model="blockhybrid",
                                      engine="python", doELBsampling=True, check_stationarity=0,
-                                     engine_roots="device"):
+                                     engine_roots="device", Compute_diagnostics=False):
     """The quasi-real-time OOS run of goVARshadowrateBlockHybrid.m:126-517 for the block-
     hybrid shadow-rate VAR, as ONE device-resident chain set per rank: every vintage
     thisT in Tjumpoffs (default: ydates > 2008-12, :127) is a data slot of the set with
@@ -796,9 +885,21 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     doELBsampling=False (the drivers' "otherwise treats fedfunds as missing data") runs the missing-data
     treatment per vintage (ccmm_chains_set_elb_treatment): shadowrateVintages* are NaN (:492) and
     missingrateVintagesMid / Tails summarise the kept draws of the censored cells, for every model.
-    Python engine only: ccmm_batch_config has no field for it."""
+    Python engine only: ccmm_batch_config has no field for it.
+
+    Compute_diagnostics=True (the switch beside check_stationarity at the top of the reference drivers,
+    goVARshadowrateBlockHybrid.m:55-56, :313-316) adds the block means of Diagnostics.m:3-25 per vintage:
+    diagSVpsrf (N x V), diagSVif (N x 3 x V; 4 / 8 / 15 % tapers), diagPAIpsrf, diagInvApsrf, diagPHIpsrf (V) and
+    diagPAIif, diagInvAif, diagPHIif (3 x V), each the per-chain value averaged over the vintage's chains (the
+    convention of shadowratePSRF).  Every kept draw then stays in the store (store_capacity = MCMCdraws, as
+    with postprocess) and Chains.diagnostics reads it in place before it is downloaded; the draws themselves do
+    not change.  MCMCdraws < 100 raises momentg's error before anything runs.  Python engine only."""
     import time
     from . import distributed as dm
+    _check_diag_draws(Compute_diagnostics, MCMCdraws)
+    if Compute_diagnostics and engine == "native":
+        raise ValueError("Compute_diagnostics runs on the Python engine (engine='python'): "
+                         "ccmm_batch_config carries no field for it")
     missing = not doELBsampling
     if missing and engine == "native":
         raise ValueError("doELBsampling=False runs on the Python engine (engine='python'): "
@@ -874,8 +975,9 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         # draw and forecast path stays on the device until the per-vintage summaries
         # (ccmm_chains_summaries) have been taken
         dev = postprocess or is_sr
+        hold = dev or bool(Compute_diagnostics)   # the store keeps every kept draw until the end
         ch, slots, yields = _bh_chain_set(ctx, us, C, seed=rndStream, ids=ids,
-                                          store_capacity=MCMCdraws if dev else chunk,
+                                          store_capacity=MCMCdraws if hold else chunk,
                                           gibbsburn=gibbsburn, ELBbound=ELBbound,
                                           ndxYIELDS=ndxYIELDS, fcstNhorizons=H, Nd=Nd,
                                           keep_paths=dev, model=model)
@@ -909,15 +1011,15 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         miss = np.empty((MCMCdraws, Ns, elbTmax, B)) if (missing and elbTmax) else None
         PAIdraws = np.empty((MCMCdraws, K, N, B)) if (keep_draws or (maxlambda and not dev_roots)) else None
         roots = np.empty((MCMCdraws, B)) if dev_roots else None   # kept draw x chain
-        post = {}
+        post, diag = {}, {}
         done = 0
         while done < MCMCdraws:
             n = min(chunk, MCMCdraws - done)
             ch.sweep(n, store=True)
-            if dev_roots and not dev:  # the chunk's stored draws, before get_draws empties the store
+            if dev_roots and not hold:  # the chunk's stored draws, before get_draws empties the store
                 for k in range(len(vidx)):
                     roots[done:done + n, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(n, C)
-            if not dev:
+            if not hold:
                 fc = ch.get_fcst()
                 if miss is not None:
                     miss[done:done + n] = ch.get_missingrate()
@@ -964,6 +1066,10 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                 if progress and (k % 8 == 7 or k == len(vidx) - 1):
                     print(f"[rank {rank}] device summaries {k + 1}/{len(vidx)} vintages "
                           f"({time.perf_counter() - t1:.1f} s)", flush=True)
+        if hold:
+            if Compute_diagnostics:  # Diagnostics.m on the stored draws, before get_draws empties the store
+                for k, i in enumerate(vidx):
+                    diag[i] = _chain_diagnostics(ch, k)
             if dev_roots:
                 for k in range(len(vidx)):
                     roots[:, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(MCMCdraws, C)
@@ -974,11 +1080,15 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
             yhsum[:] = fc["yhatsum"]
             if (is_sr and use_ps) or (missing and elbTmax):
                 miss = ch.get_missingrate()                                     # M x Ns x elbTmax x B
-            dr = ch.get_draws(which={"shadowrate_all"} | ({"PAI_all"} if PAIdraws is not None else set()))
+            need_P = PAIdraws is not None or not dev   # without the device summaries PAImean is taken here
+            dr = ch.get_draws(which={"shadowrate_all"} | ({"PAI_all"} if need_P else set()))
             if shadow is not None:
                 shadow[:] = dr["shadowrate_all"]
             if PAIdraws is not None:
                 PAIdraws[:] = dr["PAI_all"]
+            if not dev:
+                Psum += dr["PAI_all"].sum(axis=0)
+                P2sum += (dr["PAI_all"] * dr["PAI_all"]).sum(axis=0)
         status = ch.get_status()
         nacc = None
         if use_ps:
@@ -1086,6 +1196,8 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                     r["drawsMaxVARroot"] = max_var_roots(np.moveaxis(P, 3, 1).reshape(-1, K, N), N, p)
             if dev_roots:
                 r["drawsMaxVARroot"] = roots[:, cs].ravel()                 # draw slowest, chain fastest
+            for dk, dv in diag.get(i, {}).items():
+                r["diag" + dk[0].upper() + dk[1:]] = dv
             res[mine[i]] = r
             if progress and (k % 4 == 3 or k == len(vidx) - 1):
                 print(f"[rank {rank}] results {k + 1}/{len(vidx)} vintages ({time.perf_counter() - t1:.1f} s)",
@@ -1168,6 +1280,9 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                 out[nm] = np.full(shp + (V,), np.nan)
     if maxlambda:
         out["drawsMaxVARroot"] = np.full((MCMCdraws * C, V), np.nan)
+    if Compute_diagnostics:
+        for dk, shp in zip(DIAG_KEYS, ((N,), (N, 3), (), (3,), (), (3,), (), (3,))):
+            out["diag" + dk[0].upper() + dk[1:]] = np.full(shp + (V,), np.nan)
     jumpoff = p + elbT0                                                  # :497
     for v in range(V):
         r = allv.get(v)
@@ -1202,7 +1317,9 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                    "fcstYcummedian", "fcstYcumcrps", "fcstYcumquantiles", "fcstShadowYmedian",
                    "fcstShadowYquantiles", "PAImedian", "PAIquantiles", "fcstYmvlogscoreDraws",
                    "fcstYmvlogscoreXdraws", "fcstYmvlogscoreIdraws", "drawsMaxVARroot", "fcstYhatRB",
-                   "fcstYcensorhat", "fcstYcensormedian", "fcstYcensorcrps", "fcstYcensorquantiles"):
+                   "fcstYcensorhat", "fcstYcensormedian", "fcstYcensorcrps", "fcstYcensorquantiles",
+                   "diagSVpsrf", "diagSVif", "diagPAIpsrf", "diagPAIif", "diagInvApsrf", "diagInvAif",
+                   "diagPHIpsrf", "diagPHIif"):
             if nm in r and nm in out:
                 out[nm][..., v] = r[nm]
     out["fcstYhaterror"] = out["fcstYrealized"] - out["fcstYhat"]                      # :453

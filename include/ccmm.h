@@ -689,6 +689,35 @@ int ccmm_shadowrate_psrf(int M, int Ns, int elbT, int ldT, int C, const double* 
 int ccmm_shadowrate_psrf_chains(int M, int Ns, int elbT, int ldT, int C, const double* draws, const uint8_t* mask,
                                 double* out);
 
+/* Compute_diagnostics (goVARshadowrateBlockHybrid.m:55-56, :313-316): Diagnostics.m per series of kept draws.
+ * 11 statistics per series, in this order:
+ *   pmean, pstd, nse, rne, nse1, rne1, nse2, rne2, nse3, rne3  momentg (Diagnostics.m:134-300): Geweke's
+ *     numerical standard errors and relative numerical efficiencies, iid and at 4 / 8 / 15 % tapers, from
+ *     NG = 100 groups of ns = floor(M / 100) draws (draws beyond 100 ns are ignored, :190-191);
+ *     pstd, nse* = -1 where the variance estimate is not positive (:235-236, :243, :282-283)
+ *   psrf  the one-chain form of psrf (:75-85, :95-122): first against last floor(M / 3) draws
+ * The inefficiency factors of ineff (:129-132) are 1 / rne1, 1 / rne2, 1 / rne3.  A constant series gives
+ * pstd = -1 and NaN rne* and psrf (0 / 0), as the reference's arithmetic does.  The device kernel
+ * (k_diag_series: one lane per series, one coalesced pass over the draws, the 100 group means in LDS) and the
+ * host twin run the same operations in the same order and return the same bits. */
+#define CCMM_DIAG_NSTAT 11
+/* Host twin, no context and no GPU, at most 16 threads.  Series s, draw m at draws[m * ld_draw +
+ * s * ld_series]; out 11 x S, statistic k of series s at out[k * S + s].  M < 100: CCMM_ERR_ARG "momentg: needs
+ * a larger number of ndraws" (:185-187). */
+int ccmm_diagnostics_host(int M, int S, long long ld_draw, long long ld_series, const double* draws, double* out);
+/* host draws, MATLAB layout ndraw x nvar (column-major, series s at draws + s*M), uploaded in series blocks of
+ * a fixed scratch; out 11 x S as ccmm_diagnostics_host(M, S, 1, M, ..), bit for bit */
+int ccmm_diagnostics(ccmm_ctx* ctx, int M, int S, const double* draws, double* out /* 11 x S */);
+/* the stored draws of the chains bound to data slot `slot`, read in place; the store is left as it is.
+ * Needs ccmm_chains_stored >= 100 and the slot's chains contiguous (c0 .. c0 + C - 1).  source: 0 PAI
+ * (S = K N), 1 PHI (S = N (N + 1) / 2), 2 invA (S = N N; the caller selects the free elements,
+ * Diagnostics.m:19), 3 sqrtht (S = T N with T of the chain config, t fastest; rows t >= T of the slot are not
+ * computed), 4 shadow rates (shadow-rate models; S = Ns elbTmax, rate fastest; only the cells of the slot's
+ * sNaN within its elbT are computed, the cells DiagnosticsShadowrate looks at).  Entries that are not
+ * computed are NaN in all 11 statistics.  out[(k * C + c) * S + e]: statistic k, chain c0 + c, entry e, with
+ * room for 11 * C * S doubles (C <= B).  Returns C. */
+int ccmm_chains_diagnostics(ccmm_chains* ch, int source, int slot, double* out);
+
 /* Predictive density of one kept draw per chain, batched over B chains.
  * Replaces the doPredictiveDensity block mcmcVAR.m:298-381 (same simulation in
  * mcmcVARshadowrateBlockHybrid.m:550-669), including logscoreGaussian.m:15-20 and
