@@ -202,12 +202,13 @@ inline ElbCondPlan elb_cond_plan(int N, int p, int Ns) {
 inline size_t elb_gibbs_lds_bytes(int elbTmax, int Ns) {
   return (size_t)3 * elbTmax * Ns * sizeof(double) + (size_t)elbTmax * sizeof(int);
 }
-// LDS of the wavefront kernels (byte offsets): Sl [elbTmax x Ns] | Ul [W][elbTmax x Ns] | Zl [W][elbTmax x Ns]
-// | Tm [elbTmax ints] | reach [elbTmax ints] | prog [nprog ints] | one int no kernel reads
+// LDS of the wavefront kernels (byte offsets; host sizes and the kernels' pointers both come from these layouts):
+// Sl [elbTmax x Ns] | Ul [W][elbTmax x Ns] | Zl [W][elbTmax x Ns] | Tm [elbTmax ints] | reach [elbTmax ints]
+// | prog [nprog ints] | one int no kernel reads
 struct ElbWaveLds {
   size_t Sl, Ul, Zl, Tm, reach, prog, spare, end;
 };
-inline ElbWaveLds elb_wave_lds(int elbTmax, int Ns, int W, int nprog) {
+__host__ __device__ inline ElbWaveLds elb_wave_lds(int elbTmax, int Ns, int W, int nprog) {
   const size_t pg = (size_t)elbTmax * Ns * sizeof(double), I = sizeof(int);
   ElbWaveLds l{};
   l.Ul = l.Sl + pg;
@@ -220,16 +221,20 @@ inline ElbWaveLds elb_wave_lds(int elbTmax, int Ns, int W, int nprog) {
   return l;
 }
 // k_elb_gibbs_wf<NS, W, ASYNC>: W passes in flight, prog [2][W]
-inline ElbWaveLds elb_wf_lds(int elbTmax, int Ns, int W) { return elb_wave_lds(elbTmax, Ns, W, 2 * W); }
+__host__ __device__ inline ElbWaveLds elb_wf_lds(int elbTmax, int Ns, int W) {
+  return elb_wave_lds(elbTmax, Ns, W, 2 * W);
+}
 inline size_t elb_wf_lds_bytes(int elbTmax, int Ns, int W) { return elb_wf_lds(elbTmax, Ns, W).end; }
 // k_elb_gibbs_mp<NS, WPC, PARTS>: WPC drawing waves per part, prog [WPC + 1] (the drawing waves, the importer)
-inline ElbWaveLds elb_mp_lds(int elbTmax, int Ns, int WPC) { return elb_wave_lds(elbTmax, Ns, WPC, WPC + 1); }
+__host__ __device__ inline ElbWaveLds elb_mp_lds(int elbTmax, int Ns, int WPC) {
+  return elb_wave_lds(elbTmax, Ns, WPC, WPC + 1);
+}
 inline size_t elb_mp_lds_bytes(int elbTmax, int Ns, int WPC) { return elb_mp_lds(elbTmax, Ns, WPC).end; }
 // k_elb_gibbs_oct (byte offsets): Sl [elbTmax x Ns] | Tm [elbTmax ints] | reach [elbTmax ints]
 struct ElbOctLds {
   size_t Sl, Tm, reach, end;
 };
-inline ElbOctLds elb_oct_lds(int elbTmax, int Ns) {
+__host__ __device__ inline ElbOctLds elb_oct_lds(int elbTmax, int Ns) {
   ElbOctLds l{};
   l.Tm = l.Sl + (size_t)elbTmax * Ns * sizeof(double);
   l.reach = l.Tm + elbTmax * sizeof(int);

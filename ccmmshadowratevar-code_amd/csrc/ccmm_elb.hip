@@ -567,182 +567,14 @@ __device__ __forceinline__ double elb_trunc_normal_pz(double mu, double sig, dou
 
 // timing-only ablation bits of ElbDev::mode (CCMM_ELB_MODE, read by the ablation build only; a
 // default build compiles them out): 1 no draws (fmin), 2 fixed uniforms, 64 cycle attribution,
-// 128 no record loads, 256 no predecessor wait, 512 no month sums
+// 128 no record loads, 256 no predecessor wait, 512 no month sums, 4096 ub histogram of the draws
 #ifdef CCMM_ABLATION
 #define ELB_CLK(x) const unsigned long long x = (e.mode & 64) ? clock64() : 0ull
 #define ELB_ABL(bit) ((e.mode & (bit)) != 0)
-#else
-#define ELB_CLK(x) const unsigned long long x = 0ull
-#define ELB_ABL(bit) false
-#endif
-
-// ---------------------------------------------------------------- Gibbs passes (per chain)
-// One wave per chain.  Each lane owns neighbour columns lane and lane + 64 of every
-// month's record; the draws themselves run redundantly on all lanes (uniform control
-// flow).  The serial month-to-month path touches only registers and LDS: the censored
-// month list and its per-series censoring mask sit in LDS (Tm), and the next month's
-// record is prefetched from global memory into the other half of a register ping-pong
-// pair while the current month is drawn, so no global-load round trip (and no vmcnt(0)
-// wait on the prefetch) lands between two months.
-template <int NS>
-__global__ __launch_bounds__(64) void k_elb_gibbs(Dims d, ElbDev e, ChainState cs, RngArgs ra) {
-  extern __shared__ double sm[];
-  const int c = blockIdx.x;
-  const int s = cs.slot[c];
-  const int p = e.p;
-  const int T = e.elbT[s], nc = e.ncens[s];
-  if (nc == 0) return;
-  if (e.psFlag && e.psFlag[c] > 0) return;  // a PS proposal was accepted (:453-454)
-  const int lane = threadIdx.x;
-  const Rng rng = ra.make(c);
-  const int ncol = 2 * p * NS;
-  const int head = elb_cond_head(NS);
-  double* Sl = sm;                      // T x NS (t-major)
-  double* Ul = sm + T * NS;             // this pass's uniforms, T x NS (t-major)
-  double* Zl = sm + 2 * T * NS;         // their AS241 values elb_ppnd16(u) (elb_trunc_normal_pz)
-  int* Tm = (int*)(sm + 3 * T * NS);    // censored months: t | (censored-series mask << 16)
-  double* Sc = e.Scur + (size_t)c * e.elbTmax * NS;
-  const uint8_t* sN = e.sNaN + (size_t)s * e.elbTmax * NS;
-  const int* cl = e.cens + (size_t)s * e.elbTmax;
-  const double* recs = e.cond + (size_t)c * e.elbTmax * e.condStride;
-  for (int q = lane; q < T * NS; q += 64) Sl[q] = Sc[q];
-  for (int q = lane; q < nc; q += 64) {
-    const int t = cl[q];
-    int m = 0;
-    for (int a = 0; a < NS; ++a) m |= sN[t * NS + a] ? (1 << a) : 0;
-    Tm[q] = t | (m << 16);
-  }
-  __syncthreads();
-  // column geometry of this lane
-  const int c0 = lane, c1 = lane + 64;
-  const bool h0 = c0 < ncol, h1 = c1 < ncol;
-  const int kk0 = c0 / NS, sp0 = c0 % NS, kk1 = c1 / NS, sp1 = c1 % NS;
-  const int off0 = (kk0 < p) ? -(kk0 + 1) : (kk0 - p + 1);
-  const int off1 = (kk1 < p) ? -(kk1 + 1) : (kk1 - p + 1);
-  constexpr int kHd = NS + NS * (NS - 1) + 2 * NS;
-  struct Rec {
-    double hd[kHd], g0[NS], g1[NS];
-  };
-  // branch-free loads (clamped column, zeroed by select) so that the compiler's wait
-  // counting sees the prefetch as straight-line code and waits only for the older month
-  const int c0l = h0 ? c0 : 0, c1l = h1 ? c1 : 0;
-  auto load_rec = [&](int ci, Rec& r_) {
-    const double* r = recs + (size_t)ci * e.condStride;
-    for (int q = 0; q < kHd; ++q) r_.hd[q] = r[q];
-    for (int a = 0; a < NS; ++a) {
-      r_.g0[a] = r[head + c0l * NS + a];
-      r_.g1[a] = r[head + c1l * NS + a];
-    }
-  };
-  // the pass's uniforms rand(Ns, elbT) (gibbsdrawShadowrates.m:173, page n) are data
-  // independent: all lanes draw them up front (Philox pairs in parallel, or the CRN
-  // page), so no generator sits on the serial month-to-month path
-  auto uniforms = [&](int n) {
-    if (rng.crn) {
-      for (int q = lane; q < T * NS; q += 64) {
-        const double uu = rng.uniform(CCMM_RNG_ELB, (uint32_t)(q + T * NS * n));
-        Ul[q] = uu;
-        Zl[q] = elb_ppnd16(uu);
-      }
-    } else {
-      const uint32_t base = (uint32_t)(T * NS * n);  // even when T * NS is odd: handle by index
-      for (int q = 2 * lane; q < T * NS + 1; q += 128) {
-        // pair (base + q) >> 1 covers idx base+q and its partner; write both when in range
-        const uint32_t i0 = base + (uint32_t)q - ((base + (uint32_t)q) & 1u);
-        const u32x4 r = rng.raw(CCMM_RNG_ELB, i0 >> 1);
-        const int q0 = (int)(i0 - base), q1 = q0 + 1;
-        const double u0 = u01(r.x, r.y), u1 = u01(r.z, r.w);
-        if (q0 >= 0 && q0 < T * NS) {
-          Ul[q0] = u0;
-          Zl[q0] = elb_ppnd16(u0);
-        }
-        if (q1 >= 0 && q1 < T * NS) {
-          Ul[q1] = u1;
-          Zl[q1] = elb_ppnd16(u1);
-        }
-      }
-    }
-    __syncthreads();
-  };
-  // month g of the flattened (pass, month) sequence: draw from rc, prefetch month g + 1
-  // into rn; tm = Tm entry of month g, returns month g + 1's
-  const int G = e.passes * nc;
-  auto month = [&](int g, int tm, const Rec& rc, Rec& rn) -> int {
-    const int n = g / nc, ci = g - n * nc;
-    if (ci == 0) uniforms(n);
-    const int cn = (ci + 1 < nc) ? ci + 1 : 0;  // wraps to month 0 of the next pass
-    load_rec(cn, rn);  // past the last month: a harmless reload of month 0
-    const int tmn = Tm[cn];
-    const int t = tm & 0xffff, msk = tm >> 16;
-    double u[NS], zu[NS];
-    for (int a = 0; a < NS; ++a) {
-      u[a] = ELB_ABL(2) ? 0.5 : Ul[t * NS + a];
-      zu[a] = ELB_ABL(2) ? 0.0 : Zl[t * NS + a];
-    }
-    // Spost = a_t + Σ G S(neighbours)
-    const int tn0 = t + off0, tn1 = t + off1;
-    const double v0 = (h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + sp0] : 0.0;
-    const double v1 = (h1 && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + sp1] : 0.0;
-    double sp[NS];
-    for (int a = 0; a < NS; ++a) sp[a] = fma(h0 ? rc.g0[a] : 0.0, v0, (h1 ? rc.g1[a] : 0.0) * v1);
-    wave_sum_dpp_n(sp);
-    for (int a = 0; a < NS; ++a) sp[a] = rc.hd[a] + sp[a];
-    // conditional draws in index order (gibbsdrawShadowrates.m:206-218)
-    const double* beta = rc.hd + NS;
-    const double* so = beta + NS * (NS - 1);
-    double cur[NS];
-    for (int a = 0; a < NS; ++a) cur[a] = Sl[t * NS + a];
-    for (int a = 0; a < NS; ++a) {
-      if (!((msk >> a) & 1)) continue;
-      double mu = sp[a];
-      int y = 0;
-      for (int b = 0; b < NS; ++b) {
-        if (b == a) continue;
-        mu = fma(beta[a * (NS - 1) + y], cur[b] - sp[b], mu);
-        ++y;
-      }
-      uint8_t fl = 0;
-      cur[a] = ELB_ABL(1) ? fmin(mu, e.elb) : elb_trunc_normal_pz(mu, so[a], so[NS + a], e.elb, u[a], zu[a], fl);
-      if (e.flags && lane == 0)  // drawTruncNormal.m branch taken (oracle.draw_trunc_normal flags)
-        e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
-    }
-    for (int a = 0; a < NS; ++a) Sl[t * NS + a] = cur[a];
-    return tmn;
-  };
-  Rec ra_, rb_;
-  load_rec(0, ra_);
-  int tm = Tm[0];
-  for (int g = 0; g < G; g += 2) {
-    tm = month(g, tm, ra_, rb_);
-    if (g + 1 < G) tm = month(g + 1, tm, rb_, ra_);
-  }
-  __syncthreads();
-  for (int q = lane; q < T * NS; q += 64) Sc[q] = Sl[q];
-}
-
-// ---------------------------------------------------------------- Gibbs passes, wavefront
-// The same draws as k_elb_gibbs, with W passes in flight at once (one wave each).  Pass n
-// at censored month i reads the cells of months within p of t_i: the past ones as drawn
-// by pass n, the future ones and its own as drawn by pass n - 1.  So pass n may draw i
-// as soon as pass n - 1 has drawn every month up to reach(i) = max{j : t_j <= t_i + p}
-// (and pass n + 1 may then only touch months whose whole neighbourhood pass n has left):
-// the sequential order's reads are reproduced exactly, every cell sees the values it
-// sees in k_elb_gibbs, and the draws, flags and uniforms are bit-identical.  Steps run in
-// lock-step (one barrier each); progress counters are double-buffered by step parity so a
-// wave reads only what its predecessor published before the last barrier.  Within a step
-// the active months of different passes are more than p calendar months apart, so their
-// reads and writes of Sl never overlap.
-//
-// ASYNC: no per-step barrier.  Each wave runs its passes month by month, waits (acquire) until its
-// predecessor's published progress covers reach(i), draws, and publishes (release) its own; a wave
-// with less work in a month (fewer censored series) no longer waits for the slowest wave of the step.
-// The reads and writes are those of the lock-step form, so the draws stay bit-identical.
-#ifdef CCMM_ABLATION
-// timing-only attribution of the ASYNC month body (ablation build, CCMM_ELB_PROF=1): per wave,
-// shader-clock cycles spent waiting for the predecessor, in the neighbour sums, in the draws and
-// in the store/publish tail, plus the month count (read by ccmm_elb_prof)
+// 64 (CCMM_ELB_PROF=1): per wave of the ASYNC month body, shader-clock cycles spent waiting for the
+// predecessor, in the neighbour sums, in the draws and in the store/publish tail, plus the month count
 __device__ unsigned long long g_elb_prof[8 * 6];
-__device__ unsigned long long g_elb_ubhist[8];  // k_elb_gibbs_mp draws by ub = (elb - mu) / sig bin (mode 4096)
+__device__ unsigned long long g_elb_ubhist[8];  // 4096: draws by ub = (elb - mu) / sig bin
 extern "C" int ccmm_elb_ubhist(unsigned long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_elb_ubhist), sizeof(g_elb_ubhist)) != hipSuccess) return -1;
   if (reset) {
@@ -759,207 +591,403 @@ extern "C" int ccmm_elb_prof(unsigned long long* out, int reset) {
   }
   return 0;
 }
+#else
+#define ELB_CLK(x) const unsigned long long x = 0ull
+#define ELB_ABL(bit) false
 #endif
+
+// ---------------------------------------------------------------- the Gibbs kernels' shared pieces
+// Four kernels run the burnin + 1 passes of gibbsdrawShadowrates.m:171-218 under five schedules, and
+// whichever runs, draws and flags are bit-identical: every schedule gives each month's draw the same
+// inputs, and the draw itself is this one piece of code.
+//
+// The draw of censored month t in pass n: the month's record (k_elb_cond) holds a_t, the regressions
+// beta1 of each shadow rate on the others, their conditional sigmas and the 2 p Ns columns of G, one per
+// neighbour cell S(s', t ± k).  A wave's lane owns columns lane and lane + 64 (ElbCols); the wave forms
+// Spost = a_t + Σ G S(neighbours) with the fixed pairwise tree of wave_sum_dpp_n (elb_month_sums), then
+// every lane draws the month's censored rates in index order, each from its truncated normal given the
+// others' current values (elb_month_draws), redundantly and in uniform control flow.  The pass's
+// uniforms rand(Ns, elbT) (:173, page n) and their AS241 values are data independent and staged in LDS
+// before the pass (elb_pass_uniforms), the next month's record is prefetched into registers while the
+// current month is drawn (elb_load_rec), and the censored months with their per-series masks sit in LDS
+// (elb_stage), so the serial month-to-month path touches only registers and LDS.
+
+// a month's record as a lane holds it: the head a_t | beta1 | sqrtOmega1 | 1 / sqrtOmega1 and its two columns of G
+template <int NS>
+struct ElbRec {
+  static constexpr int kHd = NS + NS * (NS - 1) + 2 * NS;
+  double hd[kHd], g0[NS], g1[NS];
+};
+
+// neighbour columns c0 = lane and c1 = lane + 64 of G (col = kk Ns + s': kk < p past lag kk + 1, else future
+// lead kk - p + 1): whether they exist (h), their shadow rate (sp), their month relative to t (off) and the
+// column to load (cl: column 0 where there is none)
+struct ElbCols {
+  bool h0, h1;
+  int sp0, sp1, off0, off1, c0l, c1l;
+};
+template <int NS>
+__device__ __forceinline__ ElbCols elb_cols(int lane, int p) {
+  const int ncol = 2 * p * NS, c0 = lane, c1 = lane + 64;
+  const int kk0 = c0 / NS, kk1 = c1 / NS;
+  ElbCols g;
+  g.h0 = c0 < ncol;
+  g.h1 = c1 < ncol;
+  g.sp0 = c0 % NS;
+  g.sp1 = c1 % NS;
+  g.off0 = (kk0 < p) ? -(kk0 + 1) : (kk0 - p + 1);
+  g.off1 = (kk1 < p) ? -(kk1 + 1) : (kk1 - p + 1);
+  g.c0l = g.h0 ? c0 : 0;
+  g.c1l = g.h1 ? c1 : 0;
+  return g;
+}
+
+// branch-free loads (clamped column, zeroed by select at its use) so that the compiler's wait counting
+// sees the prefetch as straight-line code and waits only for the older month
+template <int NS>
+__device__ __forceinline__ void elb_load_rec(const ElbDev& e, const double* recs, int ci, const ElbCols& g,
+                                             ElbRec<NS>& r_) {
+  const double* r = recs + (size_t)ci * e.condStride;
+  const int head = elb_cond_head(NS);
+  for (int q = 0; q < ElbRec<NS>::kHd; ++q) r_.hd[q] = r[q];
+  for (int a = 0; a < NS; ++a) {
+    r_.g0[a] = r[head + g.c0l * NS + a];
+    r_.g1[a] = r[head + g.c1l * NS + a];
+  }
+}
+
+// staging by the workgroup's nth threads: Sl = the chain's shadow rates (T x NS, t-major), Tm[i] = t_i |
+// (censored-series mask << 16) of censored month i and, for the wavefront schedules, reach[i] =
+// max{j : t_j <= t_i + p}.  The caller issues the barrier
+template <int NS>
+__device__ __forceinline__ void elb_stage(const ElbDev& e, int c, int s, int T, int nc, int tid, int nth, double* Sl,
+                                          int* Tm, int* reach) {
+  const double* Sc = e.Scur + (size_t)c * e.elbTmax * NS;
+  const uint8_t* sN = e.sNaN + (size_t)s * e.elbTmax * NS;
+  const int* cl = e.cens + (size_t)s * e.elbTmax;
+  for (int q = tid; q < T * NS; q += nth) Sl[q] = Sc[q];
+  for (int q = tid; q < nc; q += nth) {
+    const int t = cl[q];
+    int m = 0;
+    for (int a = 0; a < NS; ++a) m |= sN[t * NS + a] ? (1 << a) : 0;
+    Tm[q] = t | (m << 16);
+    if (reach) {
+      int j = q;
+      while (j + 1 < nc && cl[j + 1] <= t + e.p) ++j;
+      reach[q] = j;
+    }
+  }
+}
+
+// pass n's uniforms (TN = T NS of them) into Ul and Zl = elb_ppnd16(Ul) (elb_trunc_normal_pz), by one
+// wave: the CRN page, or Philox pairs in parallel.  The caller issues the barrier
+__device__ __forceinline__ void elb_pass_uniforms(const Rng& rng, int n, int TN, int lane, double* Ul, double* Zl) {
+  if (rng.crn) {
+    for (int q = lane; q < TN; q += 64) {
+      const double uu = rng.uniform(CCMM_RNG_ELB, (uint32_t)(q + TN * n));
+      Ul[q] = uu;
+      Zl[q] = elb_ppnd16(uu);
+    }
+  } else {
+    const uint32_t base = (uint32_t)(TN * n);  // even when TN is odd: handle by index
+    for (int q = 2 * lane; q < TN + 1; q += 128) {
+      // pair (base + q) >> 1 covers idx base+q and its partner; write both when in range
+      const uint32_t i0 = base + (uint32_t)q - ((base + (uint32_t)q) & 1u);
+      const u32x4 r = rng.raw(CCMM_RNG_ELB, i0 >> 1);
+      const int q0 = (int)(i0 - base), q1 = q0 + 1;
+      const double u0 = u01(r.x, r.y), u1 = u01(r.z, r.w);
+      if (q0 >= 0 && q0 < TN) {
+        Ul[q0] = u0;
+        Zl[q0] = elb_ppnd16(u0);
+      }
+      if (q1 >= 0 && q1 < TN) {
+        Ul[q1] = u1;
+        Zl[q1] = elb_ppnd16(u1);
+      }
+    }
+  }
+}
+
+// one month's working values: its uniforms, their AS241 values, the month's own cells and Spost
+template <int NS>
+struct ElbMonth {
+  double u[NS], zu[NS], cur[NS], sp[NS];
+};
+
+// first half of the month body: Spost = a_t + Σ G S(neighbours), and the month's uniforms and own cells.
+// CUR_FIRST: the own cells are read with the neighbours, in one LDS round trip (the waves that wait on a
+// predecessor), not after the sums (the others: fewer live registers across the sums)
+template <int NS, bool CUR_FIRST>
+__device__ __forceinline__ void elb_month_sums(const ElbDev& e, const ElbRec<NS>& rc, const ElbCols& g,
+                                               const double* Sl, const double* Ul, const double* Zl, int t, int T,
+                                               ElbMonth<NS>& m) {
+  for (int a = 0; a < NS; ++a) {
+    m.u[a] = ELB_ABL(2) ? 0.5 : Ul[t * NS + a];
+    m.zu[a] = ELB_ABL(2) ? 0.0 : Zl[t * NS + a];
+  }
+  const int tn0 = t + g.off0, tn1 = t + g.off1;
+  const double v0 = (g.h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + g.sp0] : 0.0;
+  const double v1 = (g.h1 && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + g.sp1] : 0.0;
+  if constexpr (CUR_FIRST)
+    for (int a = 0; a < NS; ++a) m.cur[a] = Sl[t * NS + a];
+  for (int a = 0; a < NS; ++a) m.sp[a] = fma(g.h0 ? rc.g0[a] : 0.0, v0, (g.h1 ? rc.g1[a] : 0.0) * v1);
+  if (!ELB_ABL(512)) wave_sum_dpp_n(m.sp);
+  for (int a = 0; a < NS; ++a) m.sp[a] = rc.hd[a] + m.sp[a];
+  if constexpr (!CUR_FIRST)
+    for (int a = 0; a < NS; ++a) m.cur[a] = Sl[t * NS + a];
+}
+
+// second half: the conditional draws in index order (gibbsdrawShadowrates.m:206-218) from the record's
+// head hd.  draw(a, mu, sig, 1 / sig, fl) is the truncated-normal draw of rate a; rec: this lane records
+// the drawTruncNormal.m branch taken (oracle.draw_trunc_normal flags)
+template <int NS, class Draw>
+__device__ __forceinline__ void elb_month_draws(const ElbDev& e, int c, int n, int t, int msk, bool rec,
+                                                const double* hd, const double (&sp)[NS], double (&cur)[NS],
+                                                Draw draw) {
+  const double* beta = hd + NS;
+  const double* so = beta + NS * (NS - 1);
+#pragma unroll
+  for (int a = 0; a < NS; ++a) {
+    if (!((msk >> a) & 1)) continue;
+    double mu = sp[a];
+    int y = 0;
+#pragma unroll
+    for (int b = 0; b < NS; ++b) {
+      if (b == a) continue;
+      mu = fma(beta[a * (NS - 1) + y], cur[b] - sp[b], mu);
+      ++y;
+    }
+    uint8_t fl = 0;
+#ifdef CCMM_ABLATION
+    if (ELB_ABL(4096) && rec) {
+      const double ub = (e.elb - mu) * fabs(so[NS + a]);
+      const int bin = ub >= 9.0 ? 0 : ub >= 7.0 ? 1 : ub >= 5.0 ? 2 : ub >= 3.0 ? 3 : ub >= 1.0 ? 4 : ub >= -1.0 ? 5 : 6;
+      atomicAdd(&g_elb_ubhist[bin], 1ull);
+    }
+#endif
+    cur[a] = ELB_ABL(1) ? fmin(mu, e.elb) : draw(a, mu, so[a], so[NS + a], fl);
+    if (e.flags && rec) e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
+  }
+}
+
+// the wave kernels' second half: the draws with the precomputed AS241 values (lane 0 records the flags),
+// and then the month's cells back into Sl (every lane holds the same values)
+template <int NS>
+__device__ __forceinline__ void elb_month_draws_pz(const ElbDev& e, int c, int n, int t, int msk, int lane,
+                                                   const ElbRec<NS>& rc, ElbMonth<NS>& m) {
+  elb_month_draws<NS>(e, c, n, t, msk, lane == 0, rc.hd, m.sp, m.cur,
+                      [&](int a, double mu, double sig, double isig, uint8_t& fl) {
+                        return elb_trunc_normal_pz(mu, sig, isig, e.elb, m.u[a], m.zu[a], fl);
+                      });
+}
+template <int NS>
+__device__ __forceinline__ void elb_month_store(double* Sl, int t, const double (&cur)[NS]) {
+  for (int a = 0; a < NS; ++a) Sl[t * NS + a] = cur[a];
+}
+
+template <class T>
+__device__ __forceinline__ T* elb_lds(double* sm, size_t off) {  // the LDS array at a layout's byte offset
+  return (T*)((char*)sm + off);
+}
+
+// ---------------------------------------------------------------- Gibbs passes, sequential (W = 1)
+// One wave per chain runs the flattened (pass, month) sequence in order.  The next month's record goes into
+// the other half of a register ping-pong pair, so no global-load round trip (and no vmcnt(0) wait on the
+// prefetch) lands between two months.
+template <int NS>
+__global__ __launch_bounds__(64) void k_elb_gibbs(Dims d, ElbDev e, ChainState cs, RngArgs ra) {
+  extern __shared__ double sm[];
+  const int c = blockIdx.x;
+  const int s = cs.slot[c];
+  const int T = e.elbT[s], nc = e.ncens[s];
+  if (nc == 0) return;
+  if (e.psFlag && e.psFlag[c] > 0) return;  // a PS proposal was accepted (:453-454)
+  const int lane = threadIdx.x;
+  const Rng rng = ra.make(c);
+  double* Sl = sm;                      // T x NS (t-major)
+  double* Ul = sm + T * NS;             // this pass's uniforms, T x NS (t-major)
+  double* Zl = sm + 2 * T * NS;         // their AS241 values elb_ppnd16(u) (elb_trunc_normal_pz)
+  int* Tm = (int*)(sm + 3 * T * NS);    // censored months: t | (censored-series mask << 16)
+  double* Sc = e.Scur + (size_t)c * e.elbTmax * NS;
+  const double* recs = e.cond + (size_t)c * e.elbTmax * e.condStride;
+  elb_stage<NS>(e, c, s, T, nc, lane, 64, Sl, Tm, nullptr);
+  __syncthreads();
+  const ElbCols g = elb_cols<NS>(lane, e.p);
+  // month g of the flattened (pass, month) sequence: draw from rc, prefetch month g + 1
+  // into rn; tm = Tm entry of month g, returns month g + 1's
+  const int G = e.passes * nc;
+  auto month = [&](int gi, int tm, const ElbRec<NS>& rc, ElbRec<NS>& rn) -> int {
+    const int n = gi / nc, ci = gi - n * nc;
+    if (ci == 0) {
+      elb_pass_uniforms(rng, n, T * NS, lane, Ul, Zl);
+      __syncthreads();
+    }
+    const int cn = (ci + 1 < nc) ? ci + 1 : 0;  // wraps to month 0 of the next pass
+    elb_load_rec<NS>(e, recs, cn, g, rn);       // past the last month: a harmless reload of month 0
+    const int tmn = Tm[cn];
+    const int t = tm & 0xffff, msk = tm >> 16;
+    ElbMonth<NS> m;
+    elb_month_sums<NS, false>(e, rc, g, Sl, Ul, Zl, t, T, m);
+    elb_month_draws_pz<NS>(e, c, n, t, msk, lane, rc, m);
+    elb_month_store<NS>(Sl, t, m.cur);
+    return tmn;
+  };
+  ElbRec<NS> ra_, rb_;
+  elb_load_rec<NS>(e, recs, 0, g, ra_);
+  int tm = Tm[0];
+  for (int gi = 0; gi < G; gi += 2) {
+    tm = month(gi, tm, ra_, rb_);
+    if (gi + 1 < G) tm = month(gi + 1, tm, rb_, ra_);
+  }
+  __syncthreads();
+  for (int q = lane; q < T * NS; q += 64) Sc[q] = Sl[q];
+}
+
+// ---------------------------------------------------------------- Gibbs passes, wavefront
+// W passes in flight at once (one wave each).  Pass n
+// at censored month i reads the cells of months within p of t_i: the past ones as drawn
+// by pass n, the future ones and its own as drawn by pass n - 1.  So pass n may draw i
+// as soon as pass n - 1 has drawn every month up to reach(i) = max{j : t_j <= t_i + p}
+// (and pass n + 1 may then only touch months whose whole neighbourhood pass n has left):
+// the sequential order's reads are reproduced exactly, every cell sees the values it
+// sees in k_elb_gibbs, and the draws, flags and uniforms are bit-identical.  Steps run in
+// lock-step (one barrier each); progress counters are double-buffered by step parity so a
+// wave reads only what its predecessor published before the last barrier.  Within a step
+// the active months of different passes are more than p calendar months apart, so their
+// reads and writes of Sl never overlap.
+//
+// ASYNC: no per-step barrier (elb_async_passes below).  Each wave runs its passes month by month, waits
+// (acquire) until its predecessor's published progress covers reach(i), draws, and publishes (release)
+// its own; a wave with less work in a month (fewer censored series) no longer waits for the slowest wave
+// of the step.  The reads and writes are those of the lock-step form, so the draws stay bit-identical.
+
+// One wave of the asynchronous wavefront (k_elb_gibbs_wf ASYNC, the drawing waves of k_elb_gibbs_mp):
+// passes n0, n0 + W, ..., each month once *pprog, the predecessor's progress word (next draw, n nc + i),
+// covers it; its own progress goes to *oprog.  The censored-month entries are fetched two months ahead, so
+// no LDS round trip of them sits on the month's path.  Spec mode stops once the PS branch has accepted a
+// proposal.  Every spin is bounded: a stuck wave sets CCMM_STATUS_HANDOFF and publishes "done", so its
+// successors drain.  pw: the wave's row of the cycle attribution (ablation build, mode 64)
+template <int NS, int W>
+__device__ __forceinline__ void elb_async_passes(const ElbDev& e, const ChainState& cs, int c, int n0, int pw, int T,
+                                                 int nc, int lane, const Rng& rng, const double* recs, double* Sl,
+                                                 double* Ul, double* Zl, const int* Tm, const int* reach,
+                                                 const int* pprog, int* oprog) {
+  const int P = e.passes;
+  const ElbCols g = elb_cols<NS>(lane, e.p);
+  ElbRec<NS> rc, rn;
+  elb_load_rec<NS>(e, recs, 0, g, rc);
+  int tm = Tm[0], tmn = Tm[nc > 1 ? 1 : 0];
+  bool stuck = false;
+  bool aborted = false;  // spec mode: the PS branch accepted a proposal
+  int dec = 0;           // spec mode: the decision loaded four months ago
+  unsigned long long acc_w = 0, acc_s = 0, acc_d = 0, acc_t = 0, months = 0;
+  for (int n = n0; n < P && !stuck && !aborted; n += W) {
+    elb_pass_uniforms(rng, n, T * NS, lane, Ul, Zl);
+    wave_lds_sync();
+    for (int i = 0; i < nc; ++i) {
+      ELB_CLK(t0);
+      const int ni = (i + 1 < nc) ? i + 1 : 0;
+      const int nni = (ni + 1 < nc) ? ni + 1 : 0;
+      const int tmnn = Tm[nni];
+      if (!ELB_ABL(128))
+        elb_load_rec<NS>(e, recs, ni, g, rn);  // next month of this wave (month 0 of its next pass after the last)
+      else
+        rn = rc;  // (128: timing only, no record loads)
+      if (e.spec && (i & 3) == 0) {  // the PS decision, loaded after the record (in-order completion) and
+        if (dec == 1) {              // read four months later, so the poll never holds a month up
+          aborted = true;
+          break;
+        }
+        dec = elb_ps_decision(e, c);
+      }
+      if (n > 0 && !ELB_ABL(256)) {  // (256: timing only, no predecessor wait)
+        const int need = (n - 1) * nc + reach[i] + 1;
+        int it = 0;
+        while (__hip_atomic_load(pprog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) {
+          __builtin_amdgcn_s_sleep(1);
+          if (++it > (1 << 24)) {
+            stuck = true;
+            break;
+          }
+        }
+        if (stuck) break;
+      }
+      ELB_CLK(t1);
+      const int t = __builtin_amdgcn_readfirstlane(tm) & 0xffff, msk = __builtin_amdgcn_readfirstlane(tm) >> 16;
+      ElbMonth<NS> m;
+      elb_month_sums<NS, true>(e, rc, g, Sl, Ul, Zl, t, T, m);
+      ELB_CLK(t2);
+      elb_month_draws_pz<NS>(e, c, n, t, msk, lane, rc, m);
+      ELB_CLK(t3);
+      elb_month_store<NS>(Sl, t, m.cur);
+      rc = rn;
+      tm = tmn;
+      tmn = tmnn;
+      if (lane == 0) __hip_atomic_store(oprog, n * nc + i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+#ifdef CCMM_ABLATION
+      if (e.mode & 64) {
+        ELB_CLK(t4);
+        acc_w += t1 - t0;
+        acc_s += t2 - t1;
+        acc_d += t3 - t2;
+        acc_t += t4 - t3;
+        ++months;
+      }
+#endif
+    }
+  }
+#ifdef CCMM_ABLATION
+  if ((e.mode & 64) && lane == 0 && c == 0 && pw < 8) {
+    const unsigned long long acc[6] = {acc_w, acc_s, acc_d, acc_t, months, 1ull};
+    for (int q = 0; q < 6; ++q) atomicAdd(&g_elb_prof[pw * 6 + q], acc[q]);
+  }
+#endif
+  if (lane == 0) __hip_atomic_store(oprog, P * nc, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  if (stuck && lane == 0) atomicOr(&cs.status[c], CCMM_STATUS_HANDOFF);
+}
+
 template <int NS, int W, bool ASYNC>
 __global__ __launch_bounds__(64 * W) void k_elb_gibbs_wf(Dims d, ElbDev e, ChainState cs, RngArgs ra) {
   extern __shared__ double sm[];
   const int c = blockIdx.x;
   const int s = cs.slot[c];
-  const int p = e.p;
   const int T = e.elbT[s], nc = e.ncens[s];
   if (nc == 0) return;
   if (!e.spec && e.psFlag && e.psFlag[c] > 0) return;  // a PS proposal was accepted (:453-454)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const Rng rng = ra.make(c);
-  const int ncol = 2 * p * NS;
-  const int head = elb_cond_head(NS);
   const int pg = e.elbTmax * NS;
-  double* Sl = sm;                              // T x NS (t-major), shared by all passes
-  double* Ul = sm + (size_t)pg * (1 + wave);    // this wave's pass uniforms, T x NS
-  double* Zl = sm + (size_t)pg * (1 + W + wave);  // their elb_ppnd16(u) (elb_trunc_normal_pz)
-  int* Tm = (int*)(sm + (size_t)pg * (1 + 2 * W));  // censored months: t | (mask << 16)
-  int* reach = Tm + e.elbTmax;                  // reach(i)
-  int* prog = reach + e.elbTmax;                // [2][W] next draw of each wave, n nc + i
+  const ElbWaveLds L = elb_wf_lds(e.elbTmax, NS, W);
+  double* Sl = elb_lds<double>(sm, L.Sl);               // T x NS (t-major), shared by all passes
+  double* Ul = elb_lds<double>(sm, L.Ul) + pg * wave;   // this wave's pass uniforms, T x NS
+  double* Zl = elb_lds<double>(sm, L.Zl) + pg * wave;   // their elb_ppnd16(u) (elb_trunc_normal_pz)
+  int* Tm = elb_lds<int>(sm, L.Tm);                     // censored months: t | (mask << 16)
+  int* reach = elb_lds<int>(sm, L.reach);               // reach(i)
+  int* prog = elb_lds<int>(sm, L.prog);                 // [2][W] next draw of each wave, n nc + i
   double* Sc = e.Scur + (size_t)c * e.elbTmax * NS;
-  const uint8_t* sN = e.sNaN + (size_t)s * e.elbTmax * NS;
-  const int* cl = e.cens + (size_t)s * e.elbTmax;
   const double* recs = e.cond + (size_t)c * e.elbTmax * e.condStride;
   const int P = e.passes;
   const int done_all = P * nc;
-  for (int q = tid; q < T * NS; q += 64 * W) Sl[q] = Sc[q];
-  for (int q = tid; q < nc; q += 64 * W) {
-    const int t = cl[q];
-    int m = 0;
-    for (int a = 0; a < NS; ++a) m |= sN[t * NS + a] ? (1 << a) : 0;
-    Tm[q] = t | (m << 16);
-    int j = q;
-    while (j + 1 < nc && cl[j + 1] <= t + p) ++j;
-    reach[q] = j;
-  }
+  elb_stage<NS>(e, c, s, T, nc, tid, 64 * W, Sl, Tm, reach);
   if (tid < 2 * W) {
     const int w = tid % W;
     prog[tid] = (w < P) ? w * nc : done_all;
   }
   __syncthreads();
-  const int c0 = lane, c1 = lane + 64;
-  const bool h0 = c0 < ncol, h1 = c1 < ncol;
-  const int kk0 = c0 / NS, sp0 = c0 % NS, kk1 = c1 / NS, sp1 = c1 % NS;
-  const int off0 = (kk0 < p) ? -(kk0 + 1) : (kk0 - p + 1);
-  const int off1 = (kk1 < p) ? -(kk1 + 1) : (kk1 - p + 1);
-  constexpr int kHd = NS + NS * (NS - 1) + 2 * NS;
-  struct Rec {
-    double hd[kHd], g0[NS], g1[NS];
-  };
-  const int c0l = h0 ? c0 : 0, c1l = h1 ? c1 : 0;
-  auto load_rec = [&](int ci, Rec& r_) {
-    const double* r = recs + (size_t)ci * e.condStride;
-    for (int q = 0; q < kHd; ++q) r_.hd[q] = r[q];
-    for (int a = 0; a < NS; ++a) {
-      r_.g0[a] = r[head + c0l * NS + a];
-      r_.g1[a] = r[head + c1l * NS + a];
-    }
-  };
-  // pass n's uniforms rand(Ns, elbT) (gibbsdrawShadowrates.m:173, page n), drawn by this wave
-  auto uniforms = [&](int n) {
-    if (rng.crn) {
-      for (int q = lane; q < T * NS; q += 64) {
-        const double uu = rng.uniform(CCMM_RNG_ELB, (uint32_t)(q + T * NS * n));
-        Ul[q] = uu;
-        Zl[q] = elb_ppnd16(uu);
-      }
-    } else {
-      const uint32_t base = (uint32_t)(T * NS * n);
-      for (int q = 2 * lane; q < T * NS + 1; q += 128) {
-        const uint32_t i0 = base + (uint32_t)q - ((base + (uint32_t)q) & 1u);
-        const u32x4 r = rng.raw(CCMM_RNG_ELB, i0 >> 1);
-        const int q0 = (int)(i0 - base), q1 = q0 + 1;
-        const double u0 = u01(r.x, r.y), u1 = u01(r.z, r.w);
-        if (q0 >= 0 && q0 < T * NS) {
-          Ul[q0] = u0;
-          Zl[q0] = elb_ppnd16(u0);
-        }
-        if (q1 >= 0 && q1 < T * NS) {
-          Ul[q1] = u1;
-          Zl[q1] = elb_ppnd16(u1);
-        }
-      }
-    }
-    wave_lds_sync();
-  };
-  int n = wave, i = 0;
-  Rec rc, rn;
-  load_rec(0, rc);
-  int tm = Tm[0];
   if constexpr (ASYNC) {
-    // one month of pass n (the same draw code as the lock-step body below); the censored-month
-    // entries are fetched two months ahead, so no LDS round trip of them sits on the month's path
-    const int pred = (wave + W - 1) % W;
-    bool stuck = false;
-    unsigned long long acc_w = 0, acc_s = 0, acc_d = 0, acc_t = 0, months = 0;
-    int tmn = Tm[nc > 1 ? 1 : 0];
-    bool aborted = false;  // spec mode: the PS branch accepted a proposal
-    int dec = 0;           // spec mode: the decision loaded one month ago (checked one month later)
-    for (; n < P && !stuck && !aborted; n += W) {
-      uniforms(n);
-      for (i = 0; i < nc; ++i) {
-        ELB_CLK(t0);
-        const int ni = (i + 1 < nc) ? i + 1 : 0;
-        const int nni = (ni + 1 < nc) ? ni + 1 : 0;
-        const int tmnn = Tm[nni];
-        if (!ELB_ABL(128))
-          load_rec(ni, rn);  // next month of this wave (month 0 of its next pass after the last)
-        else
-          rn = rc;  // (128: timing only, no record loads)
-        if (e.spec && (i & 3) == 0) {  // the PS decision, loaded after the record (in-order completion) and
-          if (dec == 1) {              // read four months later, so the poll never holds a month up
-            aborted = true;
-            break;
-          }
-          dec = elb_ps_decision(e, c);
-        }
-        if (n > 0 && !ELB_ABL(256)) {  // (256: timing only, no predecessor wait)
-          const int need = (n - 1) * nc + reach[i] + 1;
-          int it = 0;
-          while (__hip_atomic_load(&prog[pred], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++it > (1 << 24)) {
-              stuck = true;
-              break;
-            }
-          }
-          if (stuck) break;
-        }
-        ELB_CLK(t1);
-        const int t = __builtin_amdgcn_readfirstlane(tm) & 0xffff, msk = __builtin_amdgcn_readfirstlane(tm) >> 16;
-        double u[NS], zu[NS];
-        for (int a = 0; a < NS; ++a) {
-          u[a] = ELB_ABL(2) ? 0.5 : Ul[t * NS + a];
-          zu[a] = ELB_ABL(2) ? 0.0 : Zl[t * NS + a];
-        }
-        // the neighbour cells and the month's own cells, one LDS round trip
-        const int tn0 = t + off0, tn1 = t + off1;
-        const double v0 = (h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + sp0] : 0.0;
-        const double v1 = (h1 && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + sp1] : 0.0;
-        double cur[NS];
-        for (int a = 0; a < NS; ++a) cur[a] = Sl[t * NS + a];
-        double sp[NS];
-        for (int a = 0; a < NS; ++a) sp[a] = fma(h0 ? rc.g0[a] : 0.0, v0, (h1 ? rc.g1[a] : 0.0) * v1);
-        if (!ELB_ABL(512)) wave_sum_dpp_n(sp);
-        for (int a = 0; a < NS; ++a) sp[a] = rc.hd[a] + sp[a];
-        const double* beta = rc.hd + NS;
-        const double* so = beta + NS * (NS - 1);
-        ELB_CLK(t2);
-        for (int a = 0; a < NS; ++a) {
-          if (!((msk >> a) & 1)) continue;
-          double mu = sp[a];
-          int y = 0;
-          for (int b = 0; b < NS; ++b) {
-            if (b == a) continue;
-            mu = fma(beta[a * (NS - 1) + y], cur[b] - sp[b], mu);
-            ++y;
-          }
-          uint8_t fl = 0;
-          cur[a] = ELB_ABL(1) ? fmin(mu, e.elb) : elb_trunc_normal_pz(mu, so[a], so[NS + a], e.elb, u[a], zu[a], fl);
-          if (e.flags && lane == 0)
-            e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
-        }
-        ELB_CLK(t3);
-        for (int a = 0; a < NS; ++a) Sl[t * NS + a] = cur[a];
-        rc = rn;
-        tm = tmn;
-        tmn = tmnn;
-        if (lane == 0)
-          __hip_atomic_store(&prog[wave], n * nc + i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef CCMM_ABLATION
-        if (e.mode & 64) {
-          ELB_CLK(t4);
-          acc_w += t1 - t0;
-          acc_s += t2 - t1;
-          acc_d += t3 - t2;
-          acc_t += t4 - t3;
-          ++months;
-        }
-#endif
-      }
-    }
-#ifdef CCMM_ABLATION
-    if ((e.mode & 64) && lane == 0 && c == 0 && wave < 8) {
-      atomicAdd(&g_elb_prof[wave * 6 + 0], acc_w);
-      atomicAdd(&g_elb_prof[wave * 6 + 1], acc_s);
-      atomicAdd(&g_elb_prof[wave * 6 + 2], acc_d);
-      atomicAdd(&g_elb_prof[wave * 6 + 3], acc_t);
-      atomicAdd(&g_elb_prof[wave * 6 + 4], months);
-      atomicAdd(&g_elb_prof[wave * 6 + 5], 1ull);
-    }
-#endif
-    if (lane == 0) __hip_atomic_store(&prog[wave], done_all, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (stuck && lane == 0) atomicOr(&cs.status[c], 32);
+    elb_async_passes<NS, W>(e, cs, c, wave, wave, T, nc, lane, rng, recs, Sl, Ul, Zl, Tm, reach,
+                            &prog[(wave + W - 1) % W], &prog[wave]);
     __syncthreads();
     double* dst = e.spec ? e.ScurSpec + (size_t)c * e.elbTmax * NS : Sc;  // (spec: k_elb_spec_select picks)
     for (int q = tid; q < T * NS; q += 64 * W) dst[q] = Sl[q];
     return;
   }
+  const ElbCols g = elb_cols<NS>(lane, e.p);
+  int n = wave, i = 0;
+  ElbRec<NS> rc, rn;
+  elb_load_rec<NS>(e, recs, 0, g, rc);
+  int tm = Tm[0];
   for (int step = 0;; ++step) {
     const int* prd = prog + ((step + 1) & 1) * W;  // published before the last barrier
     int* pwr = prog + (step & 1) * W;
@@ -970,46 +998,22 @@ __global__ __launch_bounds__(64 * W) void k_elb_gibbs_wf(Dims d, ElbDev e, Chain
     bool can = n < P;
     if (can && n > 0) can = prd[(wave + W - 1) % W] >= (n - 1) * nc + reach[i] + 1;
     if (can) {
-      if (i == 0) uniforms(n);
+      if (i == 0) {
+        elb_pass_uniforms(rng, n, T * NS, lane, Ul, Zl);
+        wave_lds_sync();
+      }
       int nn = n, ni = i + 1;
       if (ni == nc) {
         nn = n + W;
         ni = 0;
       }
-      load_rec(ni, rn);  // this wave's next month (a harmless reload past its last pass)
+      elb_load_rec<NS>(e, recs, ni, g, rn);  // this wave's next month (a harmless reload past its last pass)
       const int tmn = Tm[ni];
       const int t = tm & 0xffff, msk = tm >> 16;
-      double u[NS], zu[NS];
-      for (int a = 0; a < NS; ++a) {
-        u[a] = ELB_ABL(2) ? 0.5 : Ul[t * NS + a];
-        zu[a] = ELB_ABL(2) ? 0.0 : Zl[t * NS + a];
-      }
-      const int tn0 = t + off0, tn1 = t + off1;
-      const double v0 = (h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + sp0] : 0.0;
-      const double v1 = (h1 && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + sp1] : 0.0;
-      double sp[NS];
-      for (int a = 0; a < NS; ++a) sp[a] = fma(h0 ? rc.g0[a] : 0.0, v0, (h1 ? rc.g1[a] : 0.0) * v1);
-      wave_sum_dpp_n(sp);
-    for (int a = 0; a < NS; ++a) sp[a] = rc.hd[a] + sp[a];
-      const double* beta = rc.hd + NS;
-      const double* so = beta + NS * (NS - 1);
-      double cur[NS];
-      for (int a = 0; a < NS; ++a) cur[a] = Sl[t * NS + a];
-      for (int a = 0; a < NS; ++a) {
-        if (!((msk >> a) & 1)) continue;
-        double mu = sp[a];
-        int y = 0;
-        for (int b = 0; b < NS; ++b) {
-          if (b == a) continue;
-          mu = fma(beta[a * (NS - 1) + y], cur[b] - sp[b], mu);
-          ++y;
-        }
-        uint8_t fl = 0;
-        cur[a] = ELB_ABL(1) ? fmin(mu, e.elb) : elb_trunc_normal_pz(mu, so[a], so[NS + a], e.elb, u[a], zu[a], fl);
-        if (e.flags && lane == 0)
-          e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
-      }
-      for (int a = 0; a < NS; ++a) Sl[t * NS + a] = cur[a];
+      ElbMonth<NS> m;
+      elb_month_sums<NS, false>(e, rc, g, Sl, Ul, Zl, t, T, m);
+      elb_month_draws_pz<NS>(e, c, n, t, msk, lane, rc, m);
+      elb_month_store<NS>(Sl, t, m.cur);
       rc = rn;
       tm = tmn;
       n = nn;
@@ -1027,7 +1031,8 @@ __global__ __launch_bounds__(64 * W) void k_elb_gibbs_wf(Dims d, ElbDev e, Chain
 // month's draw is no longer issue-bound on a shared SIMD (the one-chain-per-vintage floor of the OOS
 // run, goVARshadowrateBlockHybrid.m:258-303, runs 8 waves on one CU otherwise).  Pass n runs on global
 // wave n mod W (part = gw / WPC).  Every part keeps its own copy of the shadow rates in LDS.
-//   within a part: the waves hand off through LDS progress words exactly as k_elb_gibbs_wf;
+//   within a part: the drawing waves run elb_async_passes and hand off through LDS progress words as in
+//   k_elb_gibbs_wf;
 //   across parts: an exporter wave of part j (wave WPC + 1) follows the LDS progress of the part's last
 //   drawing wave and publishes every cell it has drawn as a 16-byte granule {value, tag = epoch 2^16 +
 //   pass + 1}, one write-through (sc1) store each (the data is the flag; no fence), up to eight months at
@@ -1041,7 +1046,7 @@ __global__ __launch_bounds__(64 * W) void k_elb_gibbs_wf(Dims d, ElbDev e, Chain
 // import of pass n's value for m happens between those two events in the consumer part, so every read
 // sees the value the sequential order gives it: draws, flags and states are bit-identical to
 // k_elb_gibbs.  All PARTS workgroups of a chain must be resident together (the host checks occupancy);
-// every spin is bounded (status bit 32, then the wave publishes "done" so its successors drain).
+// every spin is bounded (CCMM_STATUS_HANDOFF, then the wave publishes "done" so its successors drain).
 template <int NS, int WPC, int PARTS>
 __global__ __launch_bounds__(64 * (WPC + 2)) void k_elb_gibbs_mp(Dims d, ElbDev e, ChainState cs, RngArgs ra,
                                                                  ElbXch xc) {
@@ -1049,7 +1054,6 @@ __global__ __launch_bounds__(64 * (WPC + 2)) void k_elb_gibbs_mp(Dims d, ElbDev 
   extern __shared__ double sm[];
   const int c = blockIdx.x, part = blockIdx.y;
   const int s = cs.slot[c];
-  const int p = e.p;
   const int T = e.elbT[s], nc = e.ncens[s];
   if (nc == 0) return;
   if (!e.spec && e.psFlag && e.psFlag[c] > 0) return;  // a PS proposal was accepted (:453-454)
@@ -1057,18 +1061,15 @@ __global__ __launch_bounds__(64 * (WPC + 2)) void k_elb_gibbs_mp(Dims d, ElbDev 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // WPC: the importer, WPC + 1: the exporter
   const int gw = part * WPC + wave;
   const Rng rng = ra.make(c);
-  const int ncol = 2 * p * NS;
-  const int head = elb_cond_head(NS);
   const int pg = e.elbTmax * NS;
-  double* Sl = sm;                                            // T x NS (t-major): this part's copy
-  double* Ul = sm + (size_t)pg * (1 + min(wave, WPC - 1));    // this wave's pass uniforms
-  double* Zl = sm + (size_t)pg * (1 + WPC + min(wave, WPC - 1));
-  int* Tm = (int*)(sm + (size_t)pg * (1 + 2 * WPC));          // censored months: t | (mask << 16)
-  int* reach = Tm + e.elbTmax;
-  int* prog = reach + e.elbTmax;                              // [WPC + 1]: drawing waves, importer
+  const ElbWaveLds L = elb_mp_lds(e.elbTmax, NS, WPC);
+  double* Sl = elb_lds<double>(sm, L.Sl);                                // T x NS (t-major): this part's copy
+  double* Ul = elb_lds<double>(sm, L.Ul) + pg * min(wave, WPC - 1);      // this wave's pass uniforms
+  double* Zl = elb_lds<double>(sm, L.Zl) + pg * min(wave, WPC - 1);
+  int* Tm = elb_lds<int>(sm, L.Tm);                                      // censored months: t | (mask << 16)
+  int* reach = elb_lds<int>(sm, L.reach);
+  int* prog = elb_lds<int>(sm, L.prog);                                  // [WPC + 1]: drawing waves, importer
   double* Sc = e.Scur + (size_t)c * e.elbTmax * NS;
-  const uint8_t* sN = e.sNaN + (size_t)s * e.elbTmax * NS;
-  const int* cl = e.cens + (size_t)s * e.elbTmax;
   const double* recs = e.cond + (size_t)c * e.elbTmax * e.condStride;
   const int P = e.passes;
   const int done_all = P * nc;
@@ -1078,16 +1079,7 @@ __global__ __launch_bounds__(64 * (WPC + 2)) void k_elb_gibbs_mp(Dims d, ElbDev 
   char* gbase = (char*)(xc.gran) + (size_t)c * PARTS * gstride;
   const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(gbase, 0, (int)(PARTS * gstride), 0x00020000);
   const int gout = part * (int)gstride, gin = ((part + PARTS - 1) % PARTS) * (int)gstride;
-  for (int q = tid; q < T * NS; q += 64 * (WPC + 2)) Sl[q] = Sc[q];
-  for (int q = tid; q < nc; q += 64 * (WPC + 2)) {
-    const int t = cl[q];
-    int m = 0;
-    for (int a = 0; a < NS; ++a) m |= sN[t * NS + a] ? (1 << a) : 0;
-    Tm[q] = t | (m << 16);
-    int j = q;
-    while (j + 1 < nc && cl[j + 1] <= t + p) ++j;
-    reach[q] = j;
-  }
+  elb_stage<NS>(e, c, s, T, nc, tid, 64 * (WPC + 2), Sl, Tm, reach);
   if (tid <= WPC) {
     const int g = part * WPC + tid;  // the importer's predecessor pass is gw - 1 of the part before
     prog[tid] = tid < WPC ? ((g < P) ? g * nc : done_all) : ((part * WPC - 1 + W) % W) * nc;
@@ -1187,143 +1179,9 @@ __global__ __launch_bounds__(64 * (WPC + 2)) void k_elb_gibbs_mp(Dims d, ElbDev 
     __syncthreads();
     return;
   }
-  const int c0 = lane, c1 = lane + 64;
-  const bool h0 = c0 < ncol, h1 = c1 < ncol;
-  const int kk0 = c0 / NS, sp0 = c0 % NS, kk1 = c1 / NS, sp1 = c1 % NS;
-  const int off0 = (kk0 < p) ? -(kk0 + 1) : (kk0 - p + 1);
-  const int off1 = (kk1 < p) ? -(kk1 + 1) : (kk1 - p + 1);
-  constexpr int kHd = NS + NS * (NS - 1) + 2 * NS;
-  struct Rec {
-    double hd[kHd], g0[NS], g1[NS];
-  };
-  const int c0l = h0 ? c0 : 0, c1l = h1 ? c1 : 0;
-  auto load_rec = [&](int ci, Rec& r_) {
-    const double* r = recs + (size_t)ci * e.condStride;
-    for (int q = 0; q < kHd; ++q) r_.hd[q] = r[q];
-    for (int a = 0; a < NS; ++a) {
-      r_.g0[a] = r[head + c0l * NS + a];
-      r_.g1[a] = r[head + c1l * NS + a];
-    }
-  };
-  auto uniforms = [&](int n) {  // pass n's rand(Ns, elbT) (gibbsdrawShadowrates.m:173, page n)
-    if (rng.crn) {
-      for (int q = lane; q < T * NS; q += 64) {
-        const double uu = rng.uniform(CCMM_RNG_ELB, (uint32_t)(q + T * NS * n));
-        Ul[q] = uu;
-        Zl[q] = elb_ppnd16(uu);
-      }
-    } else {
-      const uint32_t base = (uint32_t)(T * NS * n);
-      for (int q = 2 * lane; q < T * NS + 1; q += 128) {
-        const uint32_t i0 = base + (uint32_t)q - ((base + (uint32_t)q) & 1u);
-        const u32x4 r = rng.raw(CCMM_RNG_ELB, i0 >> 1);
-        const int q0 = (int)(i0 - base), q1 = q0 + 1;
-        const double u0 = u01(r.x, r.y), u1 = u01(r.z, r.w);
-        if (q0 >= 0 && q0 < T * NS) {
-          Ul[q0] = u0;
-          Zl[q0] = elb_ppnd16(u0);
-        }
-        if (q1 >= 0 && q1 < T * NS) {
-          Ul[q1] = u1;
-          Zl[q1] = elb_ppnd16(u1);
-        }
-      }
-    }
-    wave_lds_sync();
-  };
-  int* pprog = &prog[wave == 0 ? WPC : wave - 1];  // the predecessor: local wave or the importer
-  int n = gw;
-  Rec rc, rn;
-  load_rec(0, rc);
-  int tm = Tm[0];
-  bool stuck = false;
-  int tmn = Tm[nc > 1 ? 1 : 0];
-  bool aborted = false;  // spec mode: the PS branch accepted a proposal
-  int dec = 0;           // spec mode: the decision loaded one month ago
-  for (; n < P && !stuck && !aborted; n += W) {
-    uniforms(n);
-    for (int i = 0; i < nc; ++i) {
-      const int ni = (i + 1 < nc) ? i + 1 : 0;
-      const int nni = (ni + 1 < nc) ? ni + 1 : 0;
-      const int tmnn = Tm[nni];
-      load_rec(ni, rn);  // next month of this wave (month 0 of its next pass after the last)
-      if (e.spec && (i & 3) == 0) {  // the PS decision, loaded after the record, read four months later
-        if (dec == 1) {
-          aborted = true;
-          break;
-        }
-        dec = elb_ps_decision(e, c);
-      }
-      if (n > 0 && !ELB_ABL(256)) {  // (256: timing only, no predecessor wait)
-        const int need = (n - 1) * nc + reach[i] + 1;
-        int it = 0;
-        while (__hip_atomic_load(pprog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++it > (1 << 24)) {
-            stuck = true;
-            break;
-          }
-        }
-        if (stuck) break;
-      }
-      const int t = __builtin_amdgcn_readfirstlane(tm) & 0xffff, msk = __builtin_amdgcn_readfirstlane(tm) >> 16;
-      double u[NS], zu[NS];
-      for (int a = 0; a < NS; ++a) {
-        u[a] = Ul[t * NS + a];
-        zu[a] = Zl[t * NS + a];
-      }
-      const int tn0 = t + off0, tn1 = t + off1;
-      const double v0 = (h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + sp0] : 0.0;
-      const double v1 = (h1 && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + sp1] : 0.0;
-      double cur[NS];
-      for (int a = 0; a < NS; ++a) cur[a] = Sl[t * NS + a];
-      double sp[NS];
-      for (int a = 0; a < NS; ++a) sp[a] = fma(h0 ? rc.g0[a] : 0.0, v0, (h1 ? rc.g1[a] : 0.0) * v1);
-      if (ELB_ABL(1024)) {  // timing only: a second, discarded copy of the month sums on the path
-        double sq[NS];
-        for (int a = 0; a < NS; ++a) sq[a] = sp[a] * 1.0000001;
-        wave_sum_dpp_n(sq);
-        for (int a = 0; a < NS; ++a) asm volatile("" ::"v"(sq[a]));
-      }
-      wave_sum_dpp_n(sp);
-      for (int a = 0; a < NS; ++a) sp[a] = rc.hd[a] + sp[a];
-      const double* beta = rc.hd + NS;
-      const double* so = beta + NS * (NS - 1);
-      for (int a = 0; a < NS; ++a) {
-        if (!((msk >> a) & 1)) continue;
-        double mu = sp[a];
-        int y = 0;
-        for (int b = 0; b < NS; ++b) {
-          if (b == a) continue;
-          mu = fma(beta[a * (NS - 1) + y], cur[b] - sp[b], mu);
-          ++y;
-        }
-        uint8_t fl = 0;
-#ifdef CCMM_ABLATION
-        if (ELB_ABL(4096) && lane == 0) {  // ub histogram of the draws (ablation build, ccmm_elb_ubhist)
-          const double ub = (e.elb - mu) * fabs(so[NS + a]);
-          const int bin = ub >= 9.0 ? 0 : ub >= 7.0 ? 1 : ub >= 5.0 ? 2 : ub >= 3.0 ? 3 : ub >= 1.0 ? 4 : ub >= -1.0 ? 5 : 6;
-          atomicAdd(&g_elb_ubhist[bin], 1ull);
-        }
-#endif
-        cur[a] = elb_trunc_normal_pz(mu, so[a], so[NS + a], e.elb, u[a], zu[a], fl);
-        if (ELB_ABL(2048)) {  // timing only: a second, discarded draw on the path
-          uint8_t f2 = 0;
-          const double d2 = elb_trunc_normal_pz(mu * 1.0000001, so[a], so[NS + a], e.elb, u[a], zu[a], f2);
-          asm volatile("" ::"v"(d2));
-        }
-        if (e.flags && lane == 0) e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
-      }
-      for (int a = 0; a < NS; ++a) Sl[t * NS + a] = cur[a];
-      rc = rn;
-      tm = tmn;
-      tmn = tmnn;
-      if (lane == 0)
-        __hip_atomic_store(&prog[wave], n * nc + i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  }
-  if (lane == 0) __hip_atomic_store(&prog[wave], done_all, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-  if (stuck && lane == 0) atomicOr(&cs.status[c], CCMM_STATUS_HANDOFF);
+  // ---- drawing waves: pass gw, gw + W, ...; the predecessor is the local wave before, or the importer
+  elb_async_passes<NS, W>(e, cs, c, gw, gw, T, nc, lane, rng, recs, Sl, Ul, Zl, Tm, reach,
+                          &prog[wave == 0 ? WPC : wave - 1], &prog[wave]);
   __syncthreads();
   // the part that ran the last pass holds the final draw of every censored cell
   double* dst = e.spec ? e.ScurSpec + (size_t)c * e.elbTmax * NS : Sc;  // (spec: k_elb_spec_select picks)
@@ -1332,7 +1190,7 @@ __global__ __launch_bounds__(64 * (WPC + 2)) void k_elb_gibbs_mp(Dims d, ElbDev 
 }
 
 // ---------------------------------------------------------------- Gibbs passes, eight per wave
-// The wavefront of k_elb_gibbs_wf inside ONE wave: eight lanes per pass in flight ("octets": lane
+// The wavefront of k_elb_gibbs_wf inside ONE wave (option elb_oct; B >= 384 chains by default): eight lanes per pass in flight ("octets": lane
 // 8 w + j, pass slot w = 0..7 runs passes w, w + 8, ...), so the passes synchronise by cross-lane
 // shuffles instead of workgroup barriers and each truncated-normal draw is evaluated on 8 lanes
 // instead of 64 (the wave kernels are issue-bound on that redundancy from B = 256 up).  Lane j of an
@@ -1349,49 +1207,27 @@ __global__ __launch_bounds__(64) void k_elb_gibbs_oct(Dims d, ElbDev e, ChainSta
   extern __shared__ double sm[];
   const int c = blockIdx.x;
   const int s = cs.slot[c];
-  const int p = e.p;
   const int T = e.elbT[s], nc = e.ncens[s];
   if (nc == 0) return;
   if (e.psFlag && e.psFlag[c] > 0) return;  // a PS proposal was accepted (:453-454)
   const int lane = threadIdx.x;
   const int w = lane >> 3, j = lane & 7;
   const Rng rng = ra.make(c);
-  const int ncol = 2 * p * NS;
   const int head = elb_cond_head(NS);
-  double* Sl = sm;                                 // T x NS (t-major)
-  int* Tm = (int*)(sm + (size_t)e.elbTmax * NS);   // t | (mask << 16)
-  int* reach = Tm + e.elbTmax;
+  const ElbOctLds L = elb_oct_lds(e.elbTmax, NS);
+  double* Sl = elb_lds<double>(sm, L.Sl);  // T x NS (t-major)
+  int* Tm = elb_lds<int>(sm, L.Tm);        // t | (mask << 16)
+  int* reach = elb_lds<int>(sm, L.reach);
   double* Sc = e.Scur + (size_t)c * e.elbTmax * NS;
-  const uint8_t* sN = e.sNaN + (size_t)s * e.elbTmax * NS;
-  const int* cl = e.cens + (size_t)s * e.elbTmax;
   const double* recs = e.cond + (size_t)c * e.elbTmax * e.condStride;
   const int P = e.passes;
   const int done_all = P * nc;
-  for (int q = lane; q < T * NS; q += 64) Sl[q] = Sc[q];
-  for (int q = lane; q < nc; q += 64) {
-    const int t = cl[q];
-    int m = 0;
-    for (int a = 0; a < NS; ++a) m |= sN[t * NS + a] ? (1 << a) : 0;
-    Tm[q] = t | (m << 16);
-    int jj = q;
-    while (jj + 1 < nc && cl[jj + 1] <= t + p) ++jj;
-    reach[q] = jj;
-  }
+  elb_stage<NS>(e, c, s, T, nc, lane, 64, Sl, Tm, reach);
   __syncthreads();
-  // this lane's leaves: l = 8 j + m; column l (and l + 64) -> neighbour month offset and rate
-  int off0[8], sp0[8], off1[8], sp1[8];
-  bool h0[8], h1[8];
+  // this lane's leaves l = 8 j + m: columns l and l + 64, the geometry of lane l of a wave kernel
+  ElbCols g[8];
 #pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const int c0 = 8 * j + m, c1 = c0 + 64;
-    h0[m] = c0 < ncol;
-    h1[m] = c1 < ncol;
-    const int kk0 = c0 / NS, kk1 = c1 / NS;
-    sp0[m] = c0 % NS;
-    sp1[m] = c1 % NS;
-    off0[m] = (kk0 < p) ? -(kk0 + 1) : (kk0 - p + 1);
-    off1[m] = (kk1 < p) ? -(kk1 + 1) : (kk1 - p + 1);
-  }
+  for (int m = 0; m < 8; ++m) g[m] = elb_cols<NS>(8 * j + m, e.p);
   const int pred = 8 * ((w + W - 1) % W) + j;
   int n = w, i = 0;
   int prog = (n < P) ? n * nc : done_all;
@@ -1426,20 +1262,20 @@ __global__ __launch_bounds__(64) void k_elb_gibbs_oct(Dims d, ElbDev e, ChainSta
       }
       double unext[NS];
       if (nn < P) draw_u(nn, ni, unext);
-      double hd[NS + NS * (NS - 1) + 2 * NS];
+      double hd[ElbRec<NS>::kHd];
 #pragma unroll
-      for (int q = 0; q < NS + NS * (NS - 1) + 2 * NS; ++q) hd[q] = r[q];
+      for (int q = 0; q < ElbRec<NS>::kHd; ++q) hd[q] = r[q];
       double x[8][NS];
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-        const int c0 = 8 * j + m, c1 = c0 + 64;
-        const int tn0 = t + off0[m], tn1 = t + off1[m];
-        const double v0 = (h0[m] && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + sp0[m]] : 0.0;
-        const double v1 = (h1[m] && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + sp1[m]] : 0.0;
+        const ElbCols& gm = g[m];
+        const int tn0 = t + gm.off0, tn1 = t + gm.off1;
+        const double v0 = (gm.h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + gm.sp0] : 0.0;
+        const double v1 = (gm.h1 && tn1 >= 0 && tn1 < T) ? Sl[tn1 * NS + gm.sp1] : 0.0;
 #pragma unroll
         for (int a = 0; a < NS; ++a) {
-          const double g0 = h0[m] ? r[head + c0 * NS + a] : 0.0;
-          const double g1 = h1[m] ? r[head + c1 * NS + a] : 0.0;
+          const double g0 = gm.h0 ? r[head + (8 * j + m) * NS + a] : 0.0;
+          const double g1 = gm.h1 ? r[head + (8 * j + m + 64) * NS + a] : 0.0;
           x[m][a] = fma(g0, v0, g1 * v1);
         }
       }
@@ -1452,27 +1288,13 @@ __global__ __launch_bounds__(64) void k_elb_gibbs_oct(Dims d, ElbDev e, ChainSta
         v += dpp_d<0x141>(v);  // row_half_mirror: xor 4 within the octet
         sp[a] = hd[a] + v;
       }
-      // conditional draws in index order (gibbsdrawShadowrates.m:206-218)
-      const double* beta = hd + NS;
-      const double* so = beta + NS * (NS - 1);
       double cur[NS];
 #pragma unroll
       for (int a = 0; a < NS; ++a) cur[a] = Sl[t * NS + a];
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        if (!((msk >> a) & 1)) continue;
-        double mu = sp[a];
-        int y = 0;
-#pragma unroll
-        for (int b = 0; b < NS; ++b) {
-          if (b == a) continue;
-          mu = fma(beta[a * (NS - 1) + y], cur[b] - sp[b], mu);
-          ++y;
-        }
-        uint8_t fl = 0;
-        cur[a] = ELB_ABL(1) ? fmin(mu, e.elb) : elb_gibbs_trunc_normal(mu, so[a], so[NS + a], e.elb, ucur[a], fl);
-        if (e.flags && j == 0) e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
-      }
+      elb_month_draws<NS>(e, c, n, t, msk, j == 0, hd, sp, cur,
+                          [&](int a, double mu, double sig, double isig, uint8_t& fl) {
+                            return elb_gibbs_trunc_normal(mu, sig, isig, e.elb, ucur[a], fl);
+                          });
       if (j == 0) {
 #pragma unroll
         for (int a = 0; a < NS; ++a) Sl[t * NS + a] = cur[a];
@@ -1484,7 +1306,7 @@ __global__ __launch_bounds__(64) void k_elb_gibbs_oct(Dims d, ElbDev e, ChainSta
     }
     prog = (n < P) ? n * nc + i : done_all;
   }
-  if (prog < done_all && lane == 0) atomicOr(&cs.status[c], 32);  // hand-off step cap reached (ccmm.h bit 32; never expected)
+  if (prog < done_all && lane == 0) atomicOr(&cs.status[c], CCMM_STATUS_HANDOFF);  // step cap (never expected)
   __syncthreads();
   for (int q = lane; q < T * NS; q += 64) Sc[q] = Sl[q];
 }
