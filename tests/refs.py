@@ -6,7 +6,8 @@ coefficient block is the weighted-Gram algebra of CTA.m:57-98 / CTAsys.m:57-108 
 the A block one dense regression per row (mcmcVAR.m:236-254), and the SV draw one dense
 factorisation of the whole (T+1)N-square precision.  tests/test_refs.py pins the fp64 oracles to
 these within 1e-11 on every shape of tests/test_gpu_shape_edges.py.  elb_gibbs_ld is the ELB
-shadow-rate step cell by cell from the joint density of the window (tests/elb_cases.py)."""
+shadow-rate step cell by cell from the joint density of the window (tests/elb_cases.py), ps_draw_ld the joint
+draw of all censored cells of the window from the same density (tests/ps_cases.py)."""
 import numpy as np
 
 LD = np.longdouble
@@ -482,3 +483,52 @@ def girf_ld(PAI, invA, sqrtPHI, SV0, Xjumpoff, z, svz, shock11, cumcode, np_, mo
         m[cc] = np.cumsum(m[cc], axis=1) / LD(np_)
         out[sc] = m
     return out, (below / total if total else float("nan")), gap
+
+
+# ------------------------------------------------------------------ precision sampler of the censored cells (tests/ps_cases.py)
+def bwd_cols_ld(L, Y):
+    """bwd_ld on every column of Y (n x K) at once."""
+    n = Y.shape[0]
+    X = np.zeros(Y.shape, LD)
+    for k in range(n - 1, -1, -1):
+        X[k] = (Y[k] - L[k + 1:, k] @ X[k + 1:]) / L[k, k]
+    return X
+
+
+def ps_draw_ld(pai3, invbbb, Y, yNaN, Y0, pai0, z):
+    """The joint Gaussian draw of the censored cells of the window (arguments of oracle.ccmm_oracle_bh.ps_inputs /
+    precision_sampler_nan; z: n x K, one column per draw) in longdouble, read off the joint density of the
+    window as elb_gibbs_ld reads its single-cell conditionals: with the structural residuals
+    eps_t = invbbb_t (y_t - pai0_t - sum_l pai3_l y_{t-l}), t = 0..T-1 (y before month 0 from Y0), the density is
+    exp(-1/2 sum_t |eps_t|^2).  Cell i = (a, t) enters eps_t .. eps_{min(t+p, T-1)} linearly: column i of G holds
+    its slopes invbbb_t(:, a) and -invbbb_{t+k} pai3_k(:, a), so eps = e0 + G x with e0 the residuals at censored
+    cells = 0, the precision is P = G' G and the linear term b = -G' e0.  Then one dense lower Cholesky factor
+    (chol_ld) of P in month-major cell order (variables in index order within a month), ybar = L^-1 b and
+    x_k = L'^-1 (ybar + z_k).  No stacked system matrix, no band, no LAPACK.
+
+    Returns (mean P^-1 b, ybar, L, draws n x K) in longdouble and the cells as (variable, month) pairs."""
+    B = np.asarray(invbbb).astype(LD)
+    N, T = np.asarray(Y).shape
+    p = np.asarray(pai3).shape[2]
+    Phi = [np.asarray(pai3)[:, :, l].astype(LD) for l in range(p)]
+    m = np.asarray(yNaN, bool)
+    Yx = np.hstack([np.asarray(Y0).astype(LD)[:, ::-1], np.where(m, LD(0), np.asarray(Y).astype(LD))])  # column p + t: month t
+    c0 = np.asarray(pai0).astype(LD)
+    e0 = np.zeros((T, N), LD)
+    for t in range(T):
+        r = Yx[:, p + t] - c0[:, t]
+        for l in range(1, p + 1):
+            r = r - Phi[l - 1] @ Yx[:, p + t - l]
+        e0[t] = B[:, :, t] @ r
+    cells = [(a, t) for t in range(T) for a in np.nonzero(m[:, t])[0]]
+    n = len(cells)
+    G = np.zeros((T, N, n), LD)
+    for i, (a, t) in enumerate(cells):
+        G[t, :, i] = B[:, a, t]
+        for k in range(1, min(p, T - 1 - t) + 1):
+            G[t + k, :, i] = -(B[:, :, t + k] @ Phi[k - 1][:, a])
+    G = G.reshape(T * N, n)
+    L = chol_ld(G.T @ G)
+    ybar = fwd_ld(L, -(G.T @ e0.reshape(-1)))
+    zl = np.asarray(z).astype(LD).reshape(n, -1)
+    return bwd_ld(L, ybar), ybar, L, bwd_cols_ld(L, ybar[:, None] + zl), cells

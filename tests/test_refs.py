@@ -377,3 +377,66 @@ def test_bign_sweep_cta_oracle_vs_longdouble(N, p, T):
     print(f"bign sweep N={N} p={p} T={T}: coefficient block, oracle vs longdouble {e:.2e}")
     assert e < BOUND, e
     assert bgc.solve_plan(N, p, T)[0] == bgc.SWEEPS[N, p, T]
+
+
+# =============================================================================================
+# The precision sampler of the censored cells (tests/ps_cases.py; tests/test_gpu_ps_edges.py holds the device to
+# 1e-9 of refs.ps_draw_ld on these cases).  Measured, oracle.ccmm_oracle_bh.precision_sampler_nan (dense stacked
+# system, LAPACK Cholesky) against the longdouble restatement in units of max(|x|, 0.1) at the start states of
+# ps_cases.start_states: 2.7e-12 at worst (resident_last, 240 cells), every case of fewer than 100 cells below
+# 1.6e-13.  (The long-lag panels first had 60 months for 76 coefficients; the start state's regression fit then
+# interpolates, the precision loses five digits and w49_holes stood at 1.9e-9: the builder now keeps 40 months
+# more than coefficients.)
+import ps_cases as psc  # noqa: E402
+
+
+@pytest.mark.parametrize("name", psc.ALL)
+def test_ps_oracle_vs_longdouble(name):
+    c, su = psc.build(name)  # (asserts wmax, bucket, n, nc and the residency the case claims)
+    for k, ((mean, ybar, L, draws), orc) in enumerate(psc.cpu_reference(name)):
+        e = psc.rel_err(orc, draws)
+        print(f"ps {name} state {k}: n {c.n} wmax {c.wmax} bucket {c.bucket}: oracle vs longdouble {e:.2e}")
+        assert orc.shape == (c.n, 2) and e < BOUND, e
+
+
+@pytest.mark.parametrize("name", psc.ENGINEERED)
+def test_ps_engineered_proposals_clear_of_the_bound(name):
+    """Test C's normals z_k = L' x_k - ybar rounded to fp64: at the draws they produce every cell lies at least
+    0.5 from the ELB, so rounding cannot move an accept decision, and the first accepted proposal is the target."""
+    c, su = psc.build(name)
+    for k, ((_, ybar, L, _), _) in enumerate(psc.cpu_reference(name)):
+        for config, (NP, accepted, want, _) in psc.CONFIGS.items():
+            z = psc.engineered_normals(L, ybar, psc.targets(c.n, NP, accepted, early=bool(k)))
+            draws = psc.refs.bwd_cols_ld(L, ybar[:, None] + z.astype(psc.LD))
+            gap = float(np.min(np.abs(draws - psc.LD(psc.ELB))))
+            ok = np.all(draws < psc.LD(psc.ELB), axis=0)
+            assert gap >= 0.5, (name, config, gap)
+            assert (int(np.argmax(ok)) + 1 if ok.any() else 0) == want, (name, config)
+            assert int(ok.sum()) == len(accepted)
+
+
+def test_ps_cases_cover_the_edges():
+    """Where the cases land: every bucket edge and one past it, every Ns, the chunk refill on both sides, the
+    month prefix sum's second pass, the gaps around p, the window's ends, the residency threshold."""
+    C = {n: psc.case(n) for n in psc.ALL}
+    assert {c.wmax for c in C.values()} >= {1, 2, 16, 17, 32, 33, 48, 49, 64, 65, 68}
+    assert {C[n].Ns for n in psc.BAND} == {1, 2, 3, 4, 5}
+    assert {c.n for c in C.values() if c.bucket == 16} >= {1, 2, 3, 4, 5, 6, 7, 15, 16, 17, 64, 65, 128, 129}
+    assert {c.n for c in C.values() if c.bucket == 64} >= {63, 64, 65, 128, 129}
+    assert {c.nc for c in C.values() if c.Ns == 1} >= {psc.KCHUNK, psc.KCHUNK + 1}
+    assert any(c.n % 2 == 1 and c.bucket == 48 for c in (C[n] for n in psc.PHILOX))
+    for n, kp in (("gap_lag_p", 3), ("gap_p_months", 4), ("gap_p1_months", 5)):  # nearest months of the two blocks
+        t = np.nonzero(C[n].mask.any(axis=0))[0]
+        assert C[n].p == 3 and np.diff(t).max() == kp
+    assert np.diff(np.nonzero(C["gap_long"].mask.any(axis=0))[0]).max() > 2 * C["gap_long"].p
+    a = C["alternating"].mask
+    assert np.all(a.sum(axis=0)[2:10] == 1) and np.all(a[:, 2:9] != a[:, 3:10])
+    assert C["month0"].mask[:, 0].any() and C["last_month"].mask[:, -1].any()
+    assert C["month0_and_last"].mask[:, 0].any() and C["month0_and_last"].mask[:, -1].any()
+    lm = C["last_month"].mask
+    assert not np.array_equal(lm[:, -1], lm[:, -2]) and not np.array_equal(lm[:, -2], lm[:, -3])
+    r0, r1 = C["resident_last"], C["resident_first_out"]
+    assert (r0.Ns, r0.p, r0.bucket) == (r1.Ns, r1.p, r1.bucket) == (4, 15, 64)
+    assert r1.nc - r0.nc == 1 and r0.resident and not r1.resident
+    assert C["hybrid_gaps"].hybrid and sum(c.hybrid for c in C.values()) == 1
+    assert {psc.CONFIGS[k][0] for k in psc.CONFIGS} == {1, psc.BLOCK, psc.BLOCK + 1, 600}
