@@ -12,7 +12,11 @@ Every numerical step goes through ``libccmm.so``; there is no CPU fallback.
 """
 from __future__ import annotations
 
+import time
 import warnings
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 
@@ -77,9 +81,12 @@ def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATS
     res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"]]
     if doPredictiveDensity:
         res += fc
-    if B == 1:
-        res = [a[..., 0] for a in res]
-    return tuple(res)
+    return _drop_chain_axis(res, B)
+
+
+def _drop_chain_axis(res, B):
+    """The samplers' outputs as a tuple, without the trailing chain axis when there is one chain."""
+    return tuple(a[..., 0] for a in res) if B == 1 else tuple(res)
 
 
 def _run_with_predictive_density(ch, m, burn, MCMCdraws, ndxYIELDS, ELBbound, yrealized,
@@ -92,8 +99,7 @@ def _run_with_predictive_density(ch, m, burn, MCMCdraws, ndxYIELDS, ELBbound, yr
     with a trailing chain axis)."""
     N, H, B = m.N, int(fcstNhorizons), ch.B
     Nd = fcstNdraws // MCMCdraws
-    yields = np.zeros(N, bool)
-    yields[np.asarray(ndxYIELDS, int)] = True
+    yields = _mask(N, ndxYIELDS)
     y1 = np.asarray(yrealized, float).reshape(N, -1, order="F")[:, 0]
     ch.set_fcst(H, Nd, yields, keep_paths=True)
     ch.set_fcst_slot(0, y1)
@@ -108,6 +114,13 @@ def _run_with_predictive_density(ch, m, burn, MCMCdraws, ndxYIELDS, ELBbound, yr
     scores = [fc["scores"][:, :, k, :].reshape(fcstNdraws, B, order="F") for k in range(4)]
     return [fYd, fYd.mean(axis=2), fYcd, fYcd.mean(axis=2), fYs, fYs.mean(axis=2),
             fc["yhatsum"] / MCMCdraws] + scores
+
+
+def _mask(N, ndx):
+    """bool N, true at the 0-based indices ndx."""
+    m = np.zeros(N, bool)
+    m[np.asarray(ndx, int)] = True
+    return m
 
 
 def _stationarity_stats(ch, check_stationarity, stats):
@@ -189,21 +202,114 @@ def _refuse_gibbs_on_nan(where):
         "pass doELBsampleAlternate=true for the missing-data treatment")
 
 
+def _sweep_chunks(ch, burn, MCMCdraws, step):
+    """``burn`` burn-in sweeps, then ``MCMCdraws`` stored ones, at most ``step`` per call of the library.
+    Yields (store, done, n) after each chunk: it was stored or not, held n sweeps, and ``done`` sweeps of its
+    phase came before it.  Whoever iterates drains the store between the chunks, if it has to."""
+    for total, store in ((burn, False), (MCMCdraws, True)):
+        done = 0
+        while done < total:
+            n = min(step, total - done)
+            ch.sweep(n, store=store)
+            yield store, done, n
+            done += n
+
+
 def _run_chain_set(ch, burn, MCMCdraws, doprogress, step=50):
-    done = 0
-    while done < burn:
-        n = min(step, burn - done)
-        ch.sweep(n, store=False)
-        done += n
+    for store, done, n in _sweep_chunks(ch, burn, MCMCdraws, step):
         if doprogress:
-            print(f"burn-in {done}/{burn}")
-    done = 0
-    while done < MCMCdraws:
-        n = min(step, MCMCdraws - done)
-        ch.sweep(n, store=True)
-        done += n
-        if doprogress:
-            print(f"draws {done}/{MCMCdraws}")
+            print(f"draws {done + n}/{MCMCdraws}" if store else f"burn-in {done + n}/{burn}")
+
+
+@dataclass(frozen=True)
+class _Model:
+    """What differs between the ELB models.  Every driver reads these facts from _MODELS[name]; a model is one
+    row there, plus whatever it truly does differently."""
+    abi: int                 # CCMM_MODEL_* of the chain set
+    ffr_lags: bool           # build_hybrid: K = N p + 1 + Ns p (lags of the actual rates); else build_bh
+    actual_block: bool       # actualrateBlock goes to the device; else every equation is on one design
+    ps_every_sweep: bool     # PS proposals from sweep 1; else from ceil(MCMCburnin / 2)
+    ps_missingrate: bool     # the sampler's missingrate_all is proposal 1 of each PS sweep
+    linear_fcst: bool        # mcmcVARshadowrate.m:539-546: the censored recursion floors ndxOTHERYIELDS only and
+    #                          the yields are floored afterwards; its driver reports fcstYhatRB, fcstYcensor*,
+    #                          missingrateVintages*
+    Nproposals: int          # elb.Nproposals of the reference sampler
+    native: bool             # ccmm_run_batch runs it
+    maxlambda: bool          # its driver computes the maximum VAR roots
+    stationarity: bool       # check_stationarity is honoured; else warned about and ignored
+
+    def build(self, thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean, ELBbound,
+              elbT0, doRATSprior, actualrateBlock=None):
+        """Host setup of one vintage (model.build_hybrid / model.build_bh)."""
+        if self.ffr_lags:
+            return build_hybrid(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, minnesotaPriorMean, ELBbound,
+                                elbT0, doRATSprior)
+        if not self.actual_block:
+            actualrateBlock = np.zeros(np.asarray(data0).shape[1], bool)
+        return build_bh(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean,
+                        ELBbound, elbT0, doRATSprior, actualrateBlock=actualrateBlock)
+
+
+_MODELS = {
+    "blockhybrid": _Model(abi=_abi.MODEL_BLOCKHYBRID, ffr_lags=False, actual_block=True, ps_every_sweep=False,
+                          ps_missingrate=False, linear_fcst=False, Nproposals=1000, native=True, maxlambda=True,
+                          stationarity=True),
+    "hybrid": _Model(abi=_abi.MODEL_HYBRID, ffr_lags=True, actual_block=False, ps_every_sweep=True,
+                     ps_missingrate=True, linear_fcst=False, Nproposals=1000, native=True, maxlambda=False,
+                     stationarity=False),
+    "shadowrate": _Model(abi=_abi.MODEL_SHADOWRATE, ffr_lags=False, actual_block=False, ps_every_sweep=False,
+                         ps_missingrate=True, linear_fcst=True, Nproposals=100, native=False, maxlambda=True,
+                         stationarity=True),
+}
+
+
+def _run_single(model, bm, nchains, MCMCdraws, *, ndxYIELDS, ELBbound, yrealized, fcstNdraws, fcstNhorizons,
+                rndStream, doprogress, device, burnin, gibbsburn, Nproposals, elb_ps=True, missing=False,
+                alternate=False, check_stationarity=0, stats=None, want_ps=True):
+    """One vintage ``bm`` as the one-unit chain set of _bh_chain_set with C = nchains, run for the three
+    single-vintage samplers.  Returns a namespace of the raw products, each with the trailing chain axis:
+    draws (PAI_all, PHI_all, invA_all, sqrtht_all, shadowrate_all, missingrate_all; missingrate_all NaN where
+    the sweep kept none), fc (Chains.get_fcst with the paths, or None), ps (Chains.get_ps, or None when no
+    sweep proposed or ``want_ps`` is false) and yields (bool N).  ``stats`` receives stationarityRedraws."""
+    spec, m, B = _MODELS[model], bm.var, int(nchains)
+    burn = MCMCdraws if burnin is None else int(burnin)
+    dens = bool(fcstNdraws)
+    yr = np.asarray(yrealized, float).reshape(m.N, -1, order="F") if dens else None
+    ch, _, yields = _bh_chain_set(context(device), [(None, bm, yr)], B, seed=rndStream,
+                                  ids=np.arange(B, dtype=np.uint32), store_capacity=MCMCdraws,
+                                  gibbsburn=gibbsburn, ELBbound=ELBbound, ndxYIELDS=ndxYIELDS,
+                                  fcstNhorizons=int(fcstNhorizons) if dens else None,
+                                  Nd=fcstNdraws // MCMCdraws if dens else None, keep_paths=True, model=model)
+    use_ps = _bh_switches(ch, spec, burn, Nproposals=Nproposals, elb_ps=elb_ps, missing=missing,
+                          alternate=alternate, keep_missingrate=spec.ps_missingrate,
+                          check_stationarity=check_stationarity)
+    _run_chain_set(ch, burn, MCMCdraws, doprogress)
+    _stationarity_stats(ch, check_stationarity, stats)
+    ps = ch.get_ps() if use_ps and want_ps else None
+    fc = ch.get_fcst(paths=True) if dens else None
+    kept = missing or alternate or (use_ps and spec.ps_missingrate)
+    miss = ch.get_missingrate() if kept and bm.elbT else np.full((MCMCdraws, len(bm.ndxS), bm.elbT, B), np.nan)
+    out = ch.get_draws()
+    ch.close()
+    draws = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"],
+             out["shadowrate_all"][:, :, :bm.elbT], miss[:, :, :bm.elbT]]
+    return SimpleNamespace(draws=draws, fc=fc, ps=ps, yields=yields)
+
+
+def _check_fcst_draws(fcstNdraws, MCMCdraws, *needed):
+    """The samplers' checks of the predictive-density arguments; returns whether there is one."""
+    if not fcstNdraws:
+        return False
+    if fcstNdraws % MCMCdraws:
+        raise ValueError("fcstNdraws must be multiple of MCMCdraws")
+    if any(a is None for a in needed):
+        raise ValueError("predictive density needs yrealized and fcstNhorizons")
+    return True
+
+
+def _score_draws(fc, fcstNdraws, B):
+    """fcstLogscoreDraws, fcstLogscoreXdraws, fcstLogscoreIdraws (fcstNdraws x B each) of a get_fcst record."""
+    return [fc["scores"][:, :, k, :].reshape(fcstNdraws, B, order="F") for k in (1, 2, 3)]
 
 
 def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateBlock,
@@ -212,7 +318,7 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
                                  check_stationarity=0, IRF1scale=None, IRFcumcode=None,
                                  yrealized=None, fcstNdraws=None, fcstNhorizons=None,
                                  rndStream=1012023, doprogress=False, *, nchains=1, device=0,
-                                 burnin=None, gibbsburn=100, Nproposals=1000, elb_ps=True,
+                                 burnin=None, gibbsburn=100, Nproposals=_MODELS["blockhybrid"].Nproposals, elb_ps=True,
                                  stats=None):
     """mcmcVARshadowrateBlockHybrid.m:1-14, outputs PAI_all, PHI_all, invA_all,
     sqrtht_all, shadowrate_all (M x Nshadowrates x elbT), missingrate_all (NaN unless
@@ -232,80 +338,39 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     Indices are 0-based; actualrateBlock is a bool vector of length N."""
     if not doELBsampling and not doELBsampleAlternate:
         _refuse_gibbs_on_nan("mcmcVARshadowrateBlockHybrid.m:494")
-    missing = not doELBsampling
-    alternate = bool(doELBsampling and doELBsampleAlternate)
     if IRF1scale is not None:
         raise NotImplementedError("IRF outputs (doIRF1): use samplers.generateGIRF")
-    doPredictiveDensity = bool(fcstNdraws)
-    if doPredictiveDensity:
-        if fcstNdraws % MCMCdraws != 0:  # :123-126
-            raise ValueError("fcstNdraws must be multiple of MCMCdraws")
-        if yrealized is None or fcstNhorizons is None:
-            raise ValueError("predictive density needs yrealized and fcstNhorizons")
-    bm = build_bh(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
-                  minnesotaPriorMean, ELBbound, elbT0, doRATSprior,
-                  actualrateBlock=actualrateBlock)
+    doPredictiveDensity = _check_fcst_draws(fcstNdraws, MCMCdraws, yrealized, fcstNhorizons)  # :123-126
+    bm = _MODELS["blockhybrid"].build(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
+                                      minnesotaPriorMean, ELBbound, elbT0, doRATSprior, actualrateBlock)
     if bm.warn_elbT0:
-        import warnings
         warnings.warn("elbT0 + 1 should be a missing obs, but it is not ...")  # :203-205
-    m = bm.var
-    B = int(nchains)
-    burn = MCMCdraws if burnin is None else int(burnin)
-    ch = _abi.Chains(context(device), N=m.N, p=m.p, T=m.T, B=B, ndata=1, crn=False,
-                     store_capacity=MCMCdraws, seed=int(rndStream),
-                     model=_abi.MODEL_BLOCKHYBRID, Ns=len(bm.ndxS), elbTmax=bm.elbT,
-                     elb_gibbsburn=gibbsburn, elb=ELBbound)
-    ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
-    ch.set_elb_model(bm.ndxS, bm.actual_block)
-    ch.set_elb_slot(0, bm.elbT0, bm.sNaN)
-    elb_ps = bool(elb_ps and Nproposals and not missing)
-    if elb_ps:
-        ch.set_elb_ps(Nproposals, max(1, -(-burn // 2)))  # m >= MCMCburnin * .5 (:435)
-    if missing or alternate:
-        ch.set_elb_treatment(missing=missing, alternate=alternate)  # :481-499 / :470-475
-    if check_stationarity:
-        ch.set_stationarity(True)                                   # :333-347
-    st = initial_state(m, B)
-    ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
-    if doPredictiveDensity:
-        N, H = m.N, int(fcstNhorizons)
-        Nd = fcstNdraws // MCMCdraws
-        ndxYIELDS = np.union1d(bm.ndxS, bm.ndxO)                  # :83
-        yields = np.zeros(N, bool)
-        yields[ndxYIELDS] = True
-        ch.set_fcst(H, Nd, yields, keep_paths=True)
-        ch.set_fcst_slot(0, np.asarray(yrealized, float).reshape(N, -1, order="F")[:, 0])
-    _run_chain_set(ch, burn, MCMCdraws, doprogress)
-    if doPredictiveDensity:
-        fc = ch.get_fcst(paths=True)
-    _stationarity_stats(ch, check_stationarity, stats)
-    if stats is not None and elb_ps:
-        ps = ch.get_ps()
-        stats.update(countELBaccept=ps["countAccept"], countELBacceptBurnin=ps["countAcceptBurnin"],
-                     stackAccept=ps["stackAccept"])
-    miss = ch.get_missingrate() if (missing or alternate) and bm.elbT else None
-    out = ch.get_draws()
-    ch.close()
-    sr = out.get("shadowrate_all", np.full((MCMCdraws, len(bm.ndxS), 0, B), np.nan))
-    res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"], sr,
-           miss[:, :, :bm.elbT] if miss is not None else np.full((MCMCdraws, len(bm.ndxS), bm.elbT, B), np.nan)]
+    # PS from m >= MCMCburnin * .5 (:435); missing :481-499, alternate :470-475; stationarity :333-347
+    r = _run_single("blockhybrid", bm, nchains, MCMCdraws, ndxYIELDS=np.union1d(bm.ndxS, bm.ndxO),  # :83
+                    ELBbound=ELBbound, yrealized=yrealized, fcstNdraws=fcstNdraws, fcstNhorizons=fcstNhorizons,
+                    rndStream=rndStream, doprogress=doprogress, device=device, burnin=burnin,
+                    gibbsburn=gibbsburn, Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling,
+                    alternate=bool(doELBsampling and doELBsampleAlternate),
+                    check_stationarity=check_stationarity, stats=stats, want_ps=stats is not None)
+    if r.ps is not None:
+        stats.update(countELBaccept=r.ps["countAccept"], countELBacceptBurnin=r.ps["countAcceptBurnin"],
+                     stackAccept=r.ps["stackAccept"])
+    res = r.draws
     if doPredictiveDensity:
         # outputs 7-13 (:692-748): censored draws / mean, uncensored yields (shadow-rate
         # forecasts) / mean, the three one-step score draws
-        fYd = fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F")
-        fSd = fc["paths"][yields].reshape(int(yields.sum()), H, fcstNdraws, B, order="F")
-        sc = [fc["scores"][:, :, k, :].reshape(fcstNdraws, B, order="F") for k in (1, 2, 3)]
-        res += [fYd, fYd.mean(axis=2), fSd, fSd.mean(axis=2), sc[0], sc[1], sc[2]]
-    if B == 1:
-        res = [a[..., 0] for a in res]
-    return tuple(res)
+        N, H, B = bm.var.N, int(fcstNhorizons), int(nchains)
+        fYd = r.fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F")
+        fSd = r.fc["paths"][r.yields].reshape(int(r.yields.sum()), H, fcstNdraws, B, order="F")
+        res += [fYd, fYd.mean(axis=2), fSd, fSd.mean(axis=2)] + _score_draws(r.fc, fcstNdraws, B)
+    return _drop_chain_axis(res, int(nchains))
 
 
 def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATSprior,
                       doPAIactual, ndxSHADOWRATE, ndxOTHERYIELDS, doELBsampling, ELBbound, elbT0,
                       check_stationarity=0, IRF1scale=None, IRFcumcode=None, yrealized=None,
                       fcstNdraws=None, fcstNhorizons=None, rndStream=1012023, doprogress=False, *,
-                      nchains=1, device=0, burnin=None, gibbsburn=100, Nproposals=100, stats=None):
+                      nchains=1, device=0, burnin=None, gibbsburn=100, Nproposals=_MODELS["shadowrate"].Nproposals, stats=None):
     """mcmcVARshadowrate.m:1-17 (the shadow-rate VAR without the actual-rate block): CTA on
     the shadow-rate design for every equation (:322-326), the ELB step of the block hybrid
     with YHAT0 = [] (Gibbs for m < MCMCburnin/2, then elb.Nproposals = 100 PS proposals,
@@ -320,78 +385,42 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
     ``stats`` then also receives stationarityRedraws (per chain).  Indices 0-based."""
     if doPAIactual:
         raise NotImplementedError("doPAIactual = true (CTA on the actual data, :322-324) is not built")
-    missing = not doELBsampling
     if IRF1scale is not None:
         raise NotImplementedError("in-sampler IRF outputs: use samplers.generateGIRF")
-    doPredictiveDensity = bool(fcstNdraws)
-    if doPredictiveDensity and fcstNdraws % MCMCdraws:
-        raise ValueError("fcstNdraws must be multiple of MCMCdraws")
-    N = np.asarray(data0).shape[1]
-    bm = build_bh(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean,
-                  ELBbound, elbT0, doRATSprior, actualrateBlock=np.zeros(N, bool))
-    m = bm.var
-    B = int(nchains)
-    burn = MCMCdraws if burnin is None else int(burnin)
-    ch = _abi.Chains(context(device), N=m.N, p=m.p, T=m.T, B=B, ndata=1, crn=False,
-                     store_capacity=MCMCdraws, seed=int(rndStream), model=_abi.MODEL_SHADOWRATE,
-                     Ns=len(bm.ndxS), elbTmax=bm.elbT, elb_gibbsburn=gibbsburn, elb=ELBbound)
-    ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
-    ch.set_elb_model(bm.ndxS, None)
-    ch.set_elb_slot(0, bm.elbT0, bm.sNaN)
-    if missing:
-        Nproposals = 0
-        ch.set_elb_treatment(missing=True)                    # :442-459
-    if Nproposals:
-        ch.set_elb_ps(Nproposals, max(1, -(-burn // 2)))      # m >= MCMCburnin * .5 (:403)
-        ch.keep_missingrate(True)                             # missingrate = proposal 1 (:435, 498)
+    doPredictiveDensity = _check_fcst_draws(fcstNdraws, MCMCdraws)
+    bm = _MODELS["shadowrate"].build(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
+                                     minnesotaPriorMean, ELBbound, elbT0, doRATSprior)
     ndxY = np.union1d(bm.ndxS, bm.ndxO)
-    yields = np.zeros(N, bool)
-    yields[ndxY] = True
-    if doPredictiveDensity:
-        H, Nd = int(fcstNhorizons), fcstNdraws // MCMCdraws
-        ch.set_fcst(H, Nd, yields, keep_paths=True)
-        other = np.zeros(N, bool)
-        other[bm.ndxO] = True
-        ch.set_fcst_censor(other)                             # :539-546
-        ch.set_fcst_slot(0, np.asarray(yrealized, float).reshape(N, -1, order="F")[:, 0])
-    if check_stationarity:
-        ch.set_stationarity(True)
-    st = initial_state(m, B)
-    ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
-    _run_chain_set(ch, burn, MCMCdraws, doprogress)
-    _stationarity_stats(ch, check_stationarity, stats)
+    # PS from m >= MCMCburnin * .5 (:403), missingrate = proposal 1 (:435, 498); missing :442-459
+    r = _run_single("shadowrate", bm, nchains, MCMCdraws, ndxYIELDS=ndxY, ELBbound=ELBbound,
+                    yrealized=yrealized, fcstNdraws=fcstNdraws, fcstNhorizons=fcstNhorizons, rndStream=rndStream,
+                    doprogress=doprogress, device=device, burnin=burnin, gibbsburn=gibbsburn,
+                    Nproposals=Nproposals, missing=not doELBsampling, check_stationarity=check_stationarity,
+                    stats=stats)
+    B = int(nchains)
     stack = np.zeros((MCMCdraws, B), np.int32)
-    if Nproposals:
-        ps = ch.get_ps()
-        stack = ps["stackAccept"]
+    if r.ps is not None:
+        stack = r.ps["stackAccept"]
         if stats is not None:
-            stats.update(countELBaccept=ps["countAccept"], countELBacceptBurnin=ps["countAcceptBurnin"])
-    fc = ch.get_fcst(paths=True) if doPredictiveDensity else None
-    miss = ch.get_missingrate() if (Nproposals or missing) and bm.elbT else None
-    out = ch.get_draws()
-    ch.close()
-    sr = out.get("shadowrate_all", np.full((MCMCdraws, len(bm.ndxS), 0, B), np.nan))
-    res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"], sr,
-           miss[:, :, :bm.elbT] if miss is not None else np.full_like(sr, np.nan)]
+            stats.update(countELBaccept=r.ps["countAccept"], countELBacceptBurnin=r.ps["countAcceptBurnin"])
+    res = r.draws
     if doPredictiveDensity:
-        fYd = fc["paths"].reshape(N, H, fcstNdraws, B, order="F").copy()
+        N, H = bm.var.N, int(fcstNhorizons)
+        fYd = r.fc["paths"].reshape(N, H, fcstNdraws, B, order="F").copy()
         fSd = fYd[ndxY].copy()                                # fcstShadowrateDraws (:640)
         yd = fYd[ndxY]
         yd[yd < ELBbound] = ELBbound                          # :642-645
         fYd[ndxY] = yd
-        fYc = fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F").copy()
+        fYc = r.fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F").copy()
         yc = fYc[bm.ndxS]
         yc[yc < ELBbound] = ELBbound                          # :676-681
         fYc[bm.ndxS] = yc
-        RB = fc["yhatsum"] / MCMCdraws                        # :639
+        RB = r.fc["yhatsum"] / MCMCdraws                      # :639
         fYhat = RB.copy()
         fYhat[ndxY] = fYd[ndxY].mean(axis=2)                  # :683-684
-        sc = [fc["scores"][:, :, k, :].reshape(fcstNdraws, B, order="F") for k in (1, 2, 3)]
-        res += [fYd, fYhat, fYc, fYc.mean(axis=2), fSd, RB[ndxY], RB, sc[0], sc[1], sc[2]]
+        res += [fYd, fYhat, fYc, fYc.mean(axis=2), fSd, RB[ndxY], RB] + _score_draws(r.fc, fcstNdraws, B)
     res.append(stack)
-    if B == 1:
-        res = [a[..., 0] for a in res]
-    return tuple(res)
+    return _drop_chain_axis(res, B)
 
 
 def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeight,
@@ -399,7 +428,7 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
                        doELBsampleAlternate, ELBbound, elbT0, check_stationarity=0, IRF1scale=None,
                        IRFcumcode=None, yrealized=None, fcstNdraws=None, fcstNhorizons=None,
                        rndStream=1012023, doprogress=False, *, nchains=1, device=0, burnin=None,
-                       gibbsburn=100, Nproposals=1000, elb_ps=True, stats=None):
+                       gibbsburn=100, Nproposals=_MODELS["hybrid"].Nproposals, elb_ps=True, stats=None):
     """mcmcVARhybridGibbs.m:1-14, outputs PAI_all (M x K x N, K = 1 + N p + Ns p),
     PHI_all, invA_all, sqrtht_all, shadowrate_all (M x Nshadowrates x elbT),
     missingrate_all (proposal 1 of each sweep's PS draws, :486; NaN with elb_ps=False); with
@@ -413,70 +442,34 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
     em-matlabbox VARTVPSVprecisionsamplerNaN (elb_ps=False: Gibbs every sweep).
     actualrateWeight is unused, as in the reference (:16).  Indices are 0-based."""
     if check_stationarity:
-        import warnings
         warnings.warn("no stationarity check for hybrid model")  # :22-24
     if not doELBsampling and not doELBsampleAlternate:
         _refuse_gibbs_on_nan("mcmcVARhybridGibbs.m:513")
-    missing = not doELBsampling  # (doELBsampling=true ignores doELBsampleAlternate: :488-496 is commented out)
     if IRF1scale is not None:
         raise NotImplementedError("in-sampler IRF outputs: use samplers.generateGIRF(hybrid=True)")
-    doPredictiveDensity = bool(fcstNdraws)
-    if doPredictiveDensity:
-        if fcstNdraws % MCMCdraws:
-            raise ValueError("fcstNdraws must be multiple of MCMCdraws")
-        if yrealized is None or fcstNhorizons is None:
-            raise ValueError("predictive density needs yrealized and fcstNhorizons")
-    hm = build_hybrid(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, minnesotaPriorMean, ELBbound,
-                      elbT0, doRATSprior)
+    doPredictiveDensity = _check_fcst_draws(fcstNdraws, MCMCdraws, yrealized, fcstNhorizons)
+    hm = _MODELS["hybrid"].build(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
+                                 minnesotaPriorMean, ELBbound, elbT0, doRATSprior)
     if hm.warn_elbT0:
-        import warnings
         warnings.warn("elbT0 + 1 should be a missing obs, but it is not ...")  # :216-218
-    m = hm.var
-    B = int(nchains)
-    burn = MCMCdraws if burnin is None else int(burnin)
-    ch = _abi.Chains(context(device), N=m.N, p=m.p, T=m.T, B=B, ndata=1, crn=False,
-                     store_capacity=MCMCdraws, seed=int(rndStream), model=_abi.MODEL_HYBRID,
-                     Ns=len(hm.ndxS), elbTmax=hm.elbT, elb_gibbsburn=gibbsburn, elb=ELBbound)
-    ch.set_data(0, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
-    ch.set_elb_model(hm.ndxS, None)
-    ch.set_elb_slot(0, hm.elbT0, hm.sNaN)
-    elb_ps = bool(elb_ps and Nproposals and not missing)
-    if missing:
-        ch.set_elb_treatment(missing=True)             # :499-518
-    if elb_ps:
-        ch.set_elb_ps(Nproposals, 1)                   # every sweep (:458)
-        ch.keep_missingrate(True)                      # missingrate = proposal 1 (:486)
-    N = m.N
     ndxYIELDS = np.union1d(hm.ndxS, np.asarray(ndxOTHERYIELDS, int))
+    # PS at every sweep (:458), missingrate = proposal 1 (:486); missing :499-518 (doELBsampling=true ignores
+    # doELBsampleAlternate: :488-496 is commented out)
+    r = _run_single("hybrid", hm, nchains, MCMCdraws, ndxYIELDS=ndxYIELDS, ELBbound=ELBbound,
+                    yrealized=yrealized, fcstNdraws=fcstNdraws, fcstNhorizons=fcstNhorizons, rndStream=rndStream,
+                    doprogress=doprogress, device=device, burnin=burnin, gibbsburn=gibbsburn,
+                    Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling, want_ps=stats is not None)
+    if r.ps is not None:
+        stats.update(countELBaccept=r.ps["countAccept"] + r.ps["countAcceptBurnin"],
+                     stackAccept=r.ps["stackAccept"])
+    res = r.draws
     if doPredictiveDensity:
-        H, Nd = int(fcstNhorizons), fcstNdraws // MCMCdraws
-        yields = np.zeros(N, bool)
-        yields[ndxYIELDS] = True
-        ch.set_fcst(H, Nd, yields, keep_paths=True)
-        ch.set_fcst_slot(0, np.asarray(yrealized, float).reshape(N, -1, order="F")[:, 0])
-    st = initial_state(m, B)
-    ch.set_state(st["PAI"], st["A"], st["sqrtht"], st["h"], st["sqrtPHI"])
-    _run_chain_set(ch, burn, MCMCdraws, doprogress)
-    if stats is not None and elb_ps:
-        ps = ch.get_ps()
-        stats.update(countELBaccept=ps["countAccept"] + ps["countAcceptBurnin"],
-                     stackAccept=ps["stackAccept"])
-    fc = ch.get_fcst(paths=True) if doPredictiveDensity else None
-    miss = ch.get_missingrate() if (elb_ps or missing) and hm.elbT else None
-    out = ch.get_draws()
-    ch.close()
-    sr = out.get("shadowrate_all", np.full((MCMCdraws, len(hm.ndxS), 0, B), np.nan))
-    res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"], sr,
-           miss[:, :, :hm.elbT] if miss is not None else np.full((MCMCdraws, len(hm.ndxS), hm.elbT, B), np.nan)]
-    if doPredictiveDensity:
-        fYu = fc["paths"].reshape(N, H, fcstNdraws, B, order="F")          # uncensored simulation
-        fSd = fYu[ndxYIELDS].copy()                                         # fcstShadowrateDraws (:704)
-        fYd = fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F")  # yields floored (:707-711)
-        sc = [fc["scores"][:, :, k, :].reshape(fcstNdraws, B, order="F") for k in (1, 2, 3)]
-        res += [fYd, fYd.mean(axis=2), fSd, fSd.mean(axis=2), sc[0], sc[1], sc[2]]
-    if B == 1:
-        res = [a[..., 0] for a in res]
-    return tuple(res)
+        N, H, B = hm.var.N, int(fcstNhorizons), int(nchains)
+        fYu = r.fc["paths"].reshape(N, H, fcstNdraws, B, order="F")          # uncensored simulation
+        fSd = fYu[ndxYIELDS].copy()                                           # fcstShadowrateDraws (:704)
+        fYd = r.fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F")  # yields floored (:707-711)
+        res += [fYd, fYd.mean(axis=2), fSd, fSd.mean(axis=2)] + _score_draws(r.fc, fcstNdraws, B)
+    return _drop_chain_axis(res, int(nchains))
 
 
 def CTA(Y, X, N, K, T, A_, sqrtht, iV, iVb_prior, PAI, rndStream=None, *, device=0):
@@ -639,9 +632,9 @@ def goVAR_batch(data0, ydates0, Tjumpoffs, p, np_, MCMCdraws, fcstNdraws, fcstNh
     if Compute_diagnostics:
         D = S[4 + N * H:]
         o = 0
-        for k, shp in zip(DIAG_KEYS, ((N,), (N, 3), (), (3,), (), (3,), (), (3,))):
+        for name, _, shp in _diag_fields(N):
             n = int(np.prod(shp, dtype=int))
-            res["diag" + k[0].upper() + k[1:]] = D[o:o + n].reshape(shp + (D.shape[1],), order="F")
+            res[name] = D[o:o + n].reshape(shp + (D.shape[1],), order="F")
             o += n
     return res
 
@@ -740,15 +733,9 @@ def _bh_units(data0, ydates0, Tjumpoffs, p, np_, ndxSHADOWRATE, ndxOTHERYIELDS,
     mcmcVARhybridGibbs.m:33-339; model="shadowrate": mcmcVARshadowrate.m, every equation on the
     shadow-rate design) and its yrealized (goVARshadowrateBlockHybrid.m:267-283)."""
     out = []
-    N = np.asarray(data0).shape[1]
     for thisT in Tjumpoffs:
-        if model == "hybrid":
-            bm = build_hybrid(int(thisT), p, np_, data0, ydates0, ndxSHADOWRATE, minnesotaPriorMean,
-                              ELBbound, elbT0, doRATSprior)
-        else:
-            bm = build_bh(int(thisT), p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
-                          minnesotaPriorMean, ELBbound, elbT0, doRATSprior,
-                          **({"actualrateBlock": np.zeros(N, bool)} if model == "shadowrate" else {}))
+        bm = _MODELS[model].build(int(thisT), p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
+                                  minnesotaPriorMean, ELBbound, elbT0, doRATSprior)
         yr = realized_values(data0, int(thisT), fcstNhorizons, ndxSHADOWRATE, ELBbound)
         out.append((int(thisT), bm, yr))
     return out
@@ -764,21 +751,18 @@ def _bh_chain_set(ctx, units, C, *, seed, ids, store_capacity, gibbsburn, ELBbou
     Tmax = max(u[1].var.T for u in units)
     elbTmax = max(max(u[1].elbT for u in units), 1)
     B = C * len(units)
-    hybrid = model == "hybrid"
-    shadow = model == "shadowrate"
+    spec = _MODELS[model]
     ch = _abi.Chains(ctx, N=N, p=p, T=Tmax, B=B, ndata=len(units), crn=False,
-                     store_capacity=store_capacity, seed=int(seed),
-                     model=_abi.MODEL_HYBRID if hybrid else (_abi.MODEL_SHADOWRATE if shadow else _abi.MODEL_BLOCKHYBRID),
+                     store_capacity=store_capacity, seed=int(seed), model=spec.abi,
                      Ns=len(bm0.ndxS), elbTmax=elbTmax, elb_gibbsburn=gibbsburn, elb=ELBbound)
     for s, (_, bm, _) in enumerate(units):
         m = bm.var
         ch.set_data(s, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
-    ch.set_elb_model(bm0.ndxS, None if (hybrid or shadow) else bm0.actual_block)
-    yields = np.zeros(N, bool)
-    yields[np.asarray(ndxYIELDS, int)] = True
+    ch.set_elb_model(bm0.ndxS, bm0.actual_block if spec.actual_block else None)
+    yields = _mask(N, ndxYIELDS)
     if fcstNhorizons:
         ch.set_fcst(fcstNhorizons, Nd, yields, keep_paths=keep_paths)
-        if shadow:                                   # mcmcVARshadowrate.m:539-546: ndxOTHERYIELDS only
+        if spec.linear_fcst:                         # mcmcVARshadowrate.m:539-546: ndxOTHERYIELDS only
             other = yields.copy()
             other[np.asarray(bm0.ndxS, int)] = False
             ch.set_fcst_censor(other)
@@ -804,13 +788,349 @@ def _bh_chain_set(ctx, units, C, *, seed, ids, store_capacity, gibbsburn, ELBbou
     return ch, slots, yields
 
 
+def _bh_switches(ch, spec, burn, *, Nproposals, elb_ps=True, missing=False, alternate=False,
+                 keep_missingrate=False, check_stationarity=0):
+    """The per-run switches of a chain set of _bh_chain_set, for the batch and the single-vintage samplers:
+    the treatment of the ELB months (missing: doELBsampling = false, every sweep's unconstrained draw is the
+    data; alternate: one more such draw per sweep), the PS proposals from the model's first PS sweep
+    (elb_ps=False, Nproposals=0 or missing: none) with proposal 1 kept as missingrate if asked, and the
+    stationarity redraws.  Returns whether any sweep proposes."""
+    use_ps = bool(elb_ps and Nproposals and not missing)
+    if missing or alternate:
+        ch.set_elb_treatment(missing=missing, alternate=alternate)
+    if use_ps:
+        ch.set_elb_ps(Nproposals, 1 if spec.ps_every_sweep else max(1, -(-burn // 2)))
+        if keep_missingrate:
+            ch.keep_missingrate(True)
+    if check_stationarity:
+        ch.set_stationarity(True)
+    return use_ps
+
+
+class _Field(NamedTuple):
+    """One per-vintage array of the batch drivers' result: ``out[name]`` has ``shape`` plus a last axis over the
+    vintages, NaN (``fill``) where a vintage failed."""
+    name: str
+    src: str            # a device summary (Chains.summaries) of the vintage's kept draws: pa PAI, yd ydraws, yc
+    #                     ycumdraws, yz ycensordraws (shadow-rate VAR), sh shadowratedraws; or scores / logscore
+    #                     (the one-step score draws, their log mean exp), ycr (cumulated yrealized), host
+    stat: object        # of a summary: mean, stdev, median, quantiles, crps; of the scores: their column
+    shape: tuple        # in terms of K, N, H, Ny, nq, Ns, nd = fcstNdraws C, nr = MCMCdraws C
+    need: str = ""      # p: with postprocess; f: model with linear_fcst; l: with maxlambda
+    fill: float = np.nan
+
+
+_FIELDS = (
+    _Field("fcstYmvlogscore", "logscore", 1, ()), _Field("fcstYmvlogscoreX", "logscore", 2, ()),
+    _Field("fcstYmvlogscoreI", "logscore", 3, ()),
+    _Field("fcstYhat", "host", None, ("N", "H")), _Field("fcstShadowYhat", "host", None, ("Ny", "H")),
+    _Field("fcstYrealized", "host", None, ("N", "H")),
+    _Field("PAImean", "pa", "mean", ("K", "N")), _Field("PAIstdev", "pa", "stdev", ("K", "N")),
+    _Field("countELBaccept", "host", None, (), fill=-1),
+    _Field("shadowratePSRF", "host", None, ("Ns",)),                     # :213
+    _Field("shadowratePSRFchains", "host", None, ("Ns",)),               # psrf across chains (no ref.)
+    _Field("fcstYhatRB", "host", None, ("N", "H"), "f"), _Field("fcstYcensorhat", "yz", "mean", ("N", "H"), "f"),
+    _Field("fcstYmedian", "yd", "median", ("N", "H"), "p"), _Field("fcstYcrps", "yd", "crps", ("N", "H"), "p"),
+    _Field("fcstYquantiles", "yd", "quantiles", ("N", "H", "nq"), "p"),
+    _Field("fcstYcumrealized", "ycr", None, ("N", "H"), "p"), _Field("fcstYcumhat", "host", None, ("N", "H"), "p"),
+    _Field("fcstYcummedian", "yc", "median", ("N", "H"), "p"), _Field("fcstYcumcrps", "yc", "crps", ("N", "H"), "p"),
+    _Field("fcstYcumquantiles", "yc", "quantiles", ("N", "H", "nq"), "p"),
+    _Field("fcstShadowYmedian", "sh", "median", ("Ny", "H"), "p"),
+    _Field("fcstShadowYquantiles", "sh", "quantiles", ("Ny", "H", "nq"), "p"),
+    _Field("PAImedian", "pa", "median", ("K", "N"), "p"), _Field("PAIquantiles", "pa", "quantiles", ("K", "N", "nq"), "p"),
+    _Field("fcstYmvlogscoreDraws", "scores", 1, ("nd",), "p"), _Field("fcstYmvlogscoreXdraws", "scores", 2, ("nd",), "p"),
+    _Field("fcstYmvlogscoreIdraws", "scores", 3, ("nd",), "p"),
+    _Field("fcstYcensormedian", "yz", "median", ("N", "H"), "pf"), _Field("fcstYcensorcrps", "yz", "crps", ("N", "H"), "pf"),
+    _Field("fcstYcensorquantiles", "yz", "quantiles", ("N", "H", "nq"), "pf"),
+    _Field("drawsMaxVARroot", "host", None, ("nr",), "l"),
+)
+
+# forecast errors taken at the end of the run where both terms are there: name, realized, forecast
+# (goVARshadowrateBlockHybrid.m:453-454, 463-464; goVARshadowrate.m:487-488)
+_ERROR_FIELDS = (("fcstYhaterror", "fcstYrealized", "fcstYhat"),
+                 ("fcstYcensorhaterror", "fcstYrealized", "fcstYcensorhat"),
+                 ("fcstYcensormederror", "fcstYrealized", "fcstYcensormedian"),
+                 ("fcstYmederror", "fcstYrealized", "fcstYmedian"),
+                 ("fcstYcumhaterror", "fcstYcumrealized", "fcstYcumhat"),
+                 ("fcstYcummederror", "fcstYcumrealized", "fcstYcummedian"))
+
+
+def _fields(postprocess, linear_fcst, maxlambda):
+    """The rows of _FIELDS that a run with these switches fills."""
+    have = ("p" if postprocess else "") + ("f" if linear_fcst else "") + ("l" if maxlambda else "")
+    return [f for f in _FIELDS if set(f.need) <= set(have)]
+
+
+def _diag_fields(N):
+    """(result name, key of DIAG_KEYS, shape) of the Compute_diagnostics outputs of the batch drivers."""
+    return [("diag" + k[0].upper() + k[1:], k, shp)
+            for k, shp in zip(DIAG_KEYS, ((N,), (N, 3), (), (3,), (), (3,), (), (3,)))]
+
+
+def _say(b, msg):
+    if b.progress:
+        print(f"[rank {b.rank}] {msg} ({time.perf_counter() - b.t1:.1f} s)", flush=True)
+
+
+@dataclass
+class _Kept:
+    """What one attempt keeps of its chain set on the host; the chain axis (B = C per vintage) is last."""
+    scores: np.ndarray            # Nd x M x 4 x B one-step score draws
+    fYsum: np.ndarray             # N x H x B sums of the uncensored, the censored paths and of yhat
+    fYcsum: np.ndarray
+    yhsum: np.ndarray
+    Psum: np.ndarray              # K x N x B sums of PAI and PAI^2 (without the device summaries)
+    P2sum: np.ndarray
+    shadow: object                # M x Ns x elbTmax x B kept shadow rates
+    miss: object                  # the same of missingrate_all, or None
+    PAIdraws: object              # M x K x N x B (keep_draws, roots on the host), or None
+    roots: object                 # M x B maximum VAR roots from the device, or None
+    status: object = None         # B status words
+    nacc: object = None           # B accepted PS proposals, or None without PS
+
+
+def _sweep_and_keep(ch, b, nv):
+    """Burn-in and kept sweeps of one attempt (nv vintages).  Unless the store holds every kept draw (b.hold),
+    it is drained after each chunk: forecast records, missingrate and draws are downloaded and summed up, and
+    the maximum roots are taken from the chunk's stored draws before get_draws empties the store."""
+    M, C, B, elbTmax = b.MCMCdraws, b.C, ch.B, ch.elbTmax
+    acc = _Kept(scores=np.empty((b.Nd, M, 4, B)), fYsum=np.zeros((b.N, b.H, B)), fYcsum=np.zeros((b.N, b.H, B)),
+                yhsum=np.zeros((b.N, b.H, B)), Psum=np.zeros((b.K, b.N, B)), P2sum=np.zeros((b.K, b.N, B)),
+                shadow=np.empty((M, b.Ns, elbTmax, B)) if elbTmax else None,
+                miss=np.empty((M, b.Ns, elbTmax, B)) if (b.missing and elbTmax) else None,
+                PAIdraws=np.empty((M, b.K, b.N, B)) if (b.keep_draws or (b.maxlambda and not b.dev_roots)) else None,
+                roots=np.empty((M, B)) if b.dev_roots else None)   # kept draw x chain
+    for store, done, n in _sweep_chunks(ch, b.burn, M, b.chunk):
+        if store and not b.hold:
+            if b.dev_roots:
+                for k in range(nv):
+                    acc.roots[done:done + n, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(n, C)
+            fc = ch.get_fcst()
+            if acc.miss is not None:
+                acc.miss[done:done + n] = ch.get_missingrate()
+            dr = ch.get_draws(which={"PAI_all", "shadowrate_all"})
+            acc.scores[:, done:done + n] = fc["scores"]
+            acc.fYsum += fc["fYsum"]
+            acc.fYcsum += fc["fYcsum"]
+            P = dr["PAI_all"]
+            acc.Psum += P.sum(axis=0)
+            acc.P2sum += (P * P).sum(axis=0)
+            if acc.shadow is not None:
+                acc.shadow[done:done + n] = dr["shadowrate_all"]
+            if acc.PAIdraws is not None:
+                acc.PAIdraws[done:done + n] = P
+        _say(b, f"kept {done + n}/{M}" if store else f"burn-in {done + n}/{b.burn}")
+    return acc
+
+
+def _drain_held(ch, b, acc, nv, use_ps):
+    """The end of an attempt whose store held every kept draw: roots, forecast records, missingrate, draws."""
+    M, C = b.MCMCdraws, b.C
+    if b.dev_roots:
+        for k in range(nv):
+            acc.roots[:, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(M, C)
+    fc = ch.get_fcst()
+    acc.scores[:] = fc["scores"]
+    acc.fYsum[:] = fc["fYsum"]
+    acc.fYcsum[:] = fc["fYcsum"]
+    acc.yhsum[:] = fc["yhatsum"]
+    if (b.spec.linear_fcst and use_ps) or (b.missing and ch.elbTmax):
+        acc.miss = ch.get_missingrate()                                     # M x Ns x elbTmax x B
+    need_P = acc.PAIdraws is not None or not b.dev   # without the device summaries PAImean is taken here
+    dr = ch.get_draws(which={"shadowrate_all"} | ({"PAI_all"} if need_P else set()))
+    if acc.shadow is not None:
+        acc.shadow[:] = dr["shadowrate_all"]
+    if acc.PAIdraws is not None:
+        acc.PAIdraws[:] = dr["PAI_all"]
+    if not b.dev:
+        acc.Psum += dr["PAI_all"].sum(axis=0)
+        acc.P2sum += (dr["PAI_all"] * dr["PAI_all"]).sum(axis=0)
+
+
+def _vintage_summaries(ch, b, k, yr, yields):
+    """goVARshadowrateBlockHybrid.m:349-480 on the device for the vintage in data slot k: the summaries of
+    _FIELDS' sources, keyed by them, plus ycr (yrealized cumulated for ``cumcode``)."""
+    pct, cumcode = b.pct, b.cumcode
+    ycr = np.array(yr, float)
+    if cumcode is not None:
+        ycr[cumcode] = np.cumsum(ycr[cumcode], axis=1)              # :353
+    if not b.spec.linear_fcst:
+        yd = ch.summaries(1, k, realized=yr, pct=pct)                   # ydraws
+        yc = ch.summaries(1, k, cumcode=cumcode, realized=ycr, pct=pct)  # ycumdraws
+        sh = ch.summaries(0, k, rows=yields, pct=pct)                   # shadowratedraws
+        pa = ch.summaries(2, k, pct=pct)                                # PAI_all
+        return dict(yd=yd, yc=yc, sh=sh, pa=pa, ycr=ycr)
+    # goVARshadowrate.m:356-495: ydraws = uncensored paths, yields floored; the
+    # censored paths with the shadow rates floored; shadowratedraws unfloored
+    post = b.postprocess
+    q = dict(ycr=ycr, pa=ch.summaries(2, k, pct=pct if post else ()))
+    q["yd"] = ch.summaries(0, k, realized=yr if post else None, pct=pct if post else (), floor_rows=yields,
+                           floor=b.ELBbound)
+    q["yz"] = ch.summaries(1, k, realized=yr if post else None, pct=pct if post else (), floor_rows=b.smask,
+                           floor=b.ELBbound)
+    if post:
+        q["yc"] = ch.summaries(0, k, cumcode=cumcode, realized=ycr, pct=pct, floor_rows=yields, floor=b.ELBbound)
+        q["sh"] = ch.summaries(0, k, rows=yields, pct=pct)
+    return q
+
+
+def _vintage_result(b, acc, k, unit, q, diag):
+    """The result dict of the vintage in data slot k (chains k C .. (k + 1) C - 1 of ``acc``), under the names
+    of _FIELDS; q: its _vintage_summaries or None, diag: its _chain_diagnostics or {}."""
+    thisT, bm, yr = unit
+    C, N, H, K, Ns, ndxY = b.C, b.N, b.H, b.K, b.Ns, b.ndxYIELDS
+    cs = slice(k * C, (k + 1) * C)
+    nk = b.MCMCdraws * C
+    scores, shadow, miss = acc.scores, acc.shadow, acc.miss
+    r = dict(thisT=thisT, fcstYrealized=yr, countELBaccept=None if acc.nacc is None else int(acc.nacc[cs].sum()),
+             fcstYhat=acc.fYcsum[:, :, cs].sum(axis=2) / (nk * b.Nd),
+             fcstShadowYhat=acc.fYsum[ndxY][:, :, cs].sum(axis=2) / (nk * b.Nd))
+    if b.spec.linear_fcst:
+        RB = acc.yhsum[:, :, cs].sum(axis=2) / nk                          # mcmcVARshadowrate.m:639
+        yh = RB.copy()
+        yh[ndxY] = q["yd"]["mean"].reshape(N, H, order="F")[ndxY]          # :683-684
+        r.update(fcstYhat=yh, fcstYhatRB=RB, fcstShadowYhat=RB[ndxY])
+    if q is None:
+        r["PAImean"] = acc.Psum[:, :, cs].sum(axis=2) / nk
+        var = acc.P2sum[:, :, cs].sum(axis=2) / nk - r["PAImean"] ** 2
+        r["PAIstdev"] = np.sqrt(np.maximum(var, 0.0))               # std(.,1,1): 1/n
+    elif b.postprocess:
+        yh = r["fcstYhat"].copy()
+        if b.cumcode is not None:
+            yh[b.cumcode] = np.cumsum(yh[b.cumcode], axis=1)                # :355
+        r["fcstYcumhat"] = yh
+    for f in _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda):
+        if f.src == "logscore":
+            r[f.name] = _logmeanexp(scores[:, :, f.stat, cs].ravel())
+        elif f.src == "scores":
+            r[f.name] = scores[:, :, f.stat, cs].ravel(order="F")
+        elif q is not None and f.src in q:
+            r[f.name] = q[f.src] if f.stat is None else \
+                q[f.src][f.stat].reshape([b.dims[d] for d in f.shape], order="F")
+    if miss is not None and bm.elbT > 0:
+        # missingrate_all permuted to (Nobs, Ns, draws): MATLAB median (NaN if any draw
+        # is NaN) and prctile (NaN draws removed), goVARshadowrate.m:345-348
+        mr = miss[:, :, :bm.elbT, cs].transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
+        r["missingrateMid"] = np.median(mr, axis=2)
+        r["missingrateTails"] = np.moveaxis(matlab_prctile(mr, [5, 25, 75, 95], axis=2), 0, 2)
+    if shadow is not None and b.keep_draws:
+        r["shadowrate_all"] = shadow[:, :, :bm.elbT, cs].copy()     # M x Ns x elbT x C
+    if shadow is not None:
+        # goVARshadowrateBlockHybrid.m:322-325: DiagnosticsShadowrate per shadow rate over
+        # its months at the ELB, ELBdummy(startELB:thisT, s)
+        mask = b.elbdummy[b.startELB - 1:thisT].T
+        r["shadowratePSRF"] = _abi.shadowrate_psrf(shadow[..., cs], mask)
+        r["shadowratePSRFchains"] = _abi.shadowrate_psrf(shadow[..., cs], mask, chains=True)
+    if shadow is not None and bm.elbT > 0:
+        # shadowrate_all permuted to (Nobs, Ns, draws) (:329-334)
+        sr = shadow[:, :, :bm.elbT, cs].transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
+        r["shadowrateMid"] = np.median(sr, axis=2)
+        r["shadowrateTails"] = np.moveaxis(matlab_prctile(sr, [5, 25, 75, 95], axis=2), 0, 2)
+    if acc.PAIdraws is not None:
+        P = acc.PAIdraws[..., cs]
+        if b.keep_draws:
+            r["PAI_all"] = P
+        if b.maxlambda and not b.dev_roots:
+            r["drawsMaxVARroot"] = max_var_roots(np.moveaxis(P, 3, 1).reshape(-1, K, N), N, b.p)
+    if b.dev_roots:
+        r["drawsMaxVARroot"] = acc.roots[:, cs].ravel()                 # draw slowest, chain fastest
+    for name, dk, _ in _diag_fields(N):
+        if dk in diag:
+            r[name] = diag[dk]
+    return r
+
+
+def _batch_attempt(b, vidx, attempt):
+    """Run the vintages vidx (indices into b.mine) as one chain set; returns the per-vintage results (keyed by
+    global vintage index) and the list of vintages whose chains were flagged."""
+    C, mine = b.C, b.mine
+    us = [b.units[i] for i in vidx]
+    ids = np.array([(mine[i] * C + c) + attempt * 1_000_003 for i in vidx for c in range(C)],
+                   dtype=np.uint32)
+    ch, slots, yields = _bh_chain_set(b.ctx, us, C, seed=b.rndStream, ids=ids,
+                                      store_capacity=b.MCMCdraws if b.hold else b.chunk,
+                                      gibbsburn=b.gibbsburn, ELBbound=b.ELBbound,
+                                      ndxYIELDS=b.ndxYIELDS, fcstNhorizons=b.H, Nd=b.Nd,
+                                      keep_paths=b.dev, model=b.model)
+    # PS: block hybrid, shadow rate from m >= MCMCburnin * .5 (:435, mcmcVARshadowrate.m:403), hybrid at every
+    # sweep (mcmcVARhybridGibbs.m:458); missingrate kept where the driver reports it (mcmcVARshadowrate.m:435, 498)
+    use_ps = _bh_switches(ch, b.spec, b.burn, Nproposals=b.Nproposals, elb_ps=b.elb_ps, missing=b.missing,
+                          keep_missingrate=b.spec.linear_fcst, check_stationarity=b.check_stationarity)
+    acc = _sweep_and_keep(ch, b, len(vidx))
+    post, diag = {}, {}
+    if b.dev:
+        for k, i in enumerate(vidx):
+            post[i] = _vintage_summaries(ch, b, k, us[k][2], yields)
+            if k % 8 == 7 or k == len(vidx) - 1:
+                _say(b, f"device summaries {k + 1}/{len(vidx)} vintages")
+    if b.hold:
+        if b.diagnostics:  # Diagnostics.m on the stored draws, before get_draws empties the store
+            for k, i in enumerate(vidx):
+                diag[i] = _chain_diagnostics(ch, k)
+        _drain_held(ch, b, acc, len(vidx), use_ps)
+    acc.status = ch.get_status()
+    if use_ps:
+        psd = ch.get_ps()
+        acc.nacc = psd["countAccept"] + psd["countAcceptBurnin"]
+    ch.close()
+    res, failed = {}, []
+    for k, i in enumerate(vidx):
+        if np.any(acc.status[k * C:(k + 1) * C] & ~_abi.STATUS_INFO):  # bits 1, 64: informational (valid draws)
+            failed.append(i)
+            continue
+        res[mine[i]] = _vintage_result(b, acc, k, us[k], post.get(i), diag.get(i, {}))
+        if k % 4 == 3 or k == len(vidx) - 1:
+            _say(b, f"results {k + 1}/{len(vidx)} vintages")
+    return res, failed
+
+
+def _batch_out(b, allv, Tjumpoffs, assignment, Tdata, jumpoff):
+    """The end-of-run assembly: every per-vintage result of ``allv`` (None: the vintage failed) into arrays
+    with the vintage last, by _FIELDS, then the forecast errors."""
+    V, Ns = len(Tjumpoffs), b.Ns
+    out = dict(Tjumpoffs=np.array(Tjumpoffs), assignment=assignment)
+    fields = _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda)
+    for f in fields:
+        out[f.name] = np.full(tuple(b.dims[d] for d in f.shape) + (V,), f.fill)
+    windows = ("shadowrate",) + (("missingrate",) if b.spec.linear_fcst or b.missing else ())
+    for w in windows:                                  # months x Ns: median, prctile [5 25 75 95]
+        out[w + "VintagesMid"] = np.full((Tdata, Ns, V), np.nan)
+        out[w + "VintagesTails"] = np.full((Tdata, Ns, 4, V), np.nan)
+    kept = ("PAI_all", "shadowrate_all") if b.keep_draws else ()
+    for nm in kept:
+        out[nm] = {}
+    diags = _diag_fields(b.N) if b.diagnostics else ()
+    for nm, _, shp in diags:
+        out[nm] = np.full(shp + (V,), np.nan)
+    for v in range(V):
+        r = allv.get(v)
+        if r is None:
+            continue
+        for nm in [f.name for f in fields] + [d[0] for d in diags]:
+            if r.get(nm) is not None:
+                out[nm][..., v] = r[nm]
+        for w in windows:
+            if w + "Mid" in r:                         # :497-506, goVARshadowrate.m:523-529
+                out[w + "VintagesMid"][jumpoff:r["thisT"], :, v] = r[w + "Mid"]
+                out[w + "VintagesTails"][jumpoff:r["thisT"], :, :, v] = r[w + "Tails"]
+        for nm in kept:
+            if nm in r:
+                out[nm][v] = r[nm]
+    for nm, real, fc in _ERROR_FIELDS:
+        if real in out and fc in out:
+            out[nm] = out[real] - out[fc]
+    if b.postprocess:
+        out["setQuantiles"] = b.pct
+    return out
+
+
 def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
                                      minnesotaPriorMean, *, Tjumpoffs=None, p=12, np_=12,
                                      MCMCdraws=1000, fcstNdraws=None, fcstNhorizons=48,
                                      ELBbound=0.25, doRATSprior=True, nchains=1, burnin=None,
                                      gibbsburn=100, rndStream=1012023, dist=None, device=None,
                                      chunk=50, max_retries=2, keep_draws=False, progress=False,
-                                     Nproposals=1000, elb_ps=True, postprocess=False, cumcode=None,
+                                     Nproposals=_MODELS["blockhybrid"].Nproposals, elb_ps=True, postprocess=False, cumcode=None,
                                      setQuantiles=None, maxlambda=False, model="blockhybrid",
                                      engine="python", doELBsampling=True, check_stationarity=0,
                                      engine_roots="device", Compute_diagnostics=False):
@@ -894,7 +1214,6 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     convention of shadowratePSRF).  Every kept draw then stays in the store (store_capacity = MCMCdraws, as
     with postprocess) and Chains.diagnostics reads it in place before it is downloaded; the draws themselves do
     not change.  MCMCdraws < 100 raises momentg's error before anything runs.  Python engine only."""
-    import time
     from . import distributed as dm
     _check_diag_draws(Compute_diagnostics, MCMCdraws)
     if Compute_diagnostics and engine == "native":
@@ -917,7 +1236,6 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         fcstNdraws = 10 * MCMCdraws                                      # :38
     if fcstNdraws % MCMCdraws:
         raise ValueError("fcstNdraws must be multiple of MCMCdraws")     # :123-126
-    Nd = fcstNdraws // MCMCdraws
     burn = MCMCdraws if burnin is None else int(burnin)
     C = int(nchains)
     H = int(fcstNhorizons)
@@ -927,28 +1245,23 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     rank = dist.get_rank() if dist is not None else 0
     size = dist.get_world_size() if dist is not None else 1
     device = _rank_device(dist, device)
-    hybrid = model == "hybrid"
-    is_sr = model == "shadowrate"
-    if model not in ("blockhybrid", "hybrid", "shadowrate"):
+    spec = _MODELS.get(model)
+    if spec is None:
         raise ValueError(f"unknown model {model!r}")
-    if is_sr and engine == "native":
-        raise ValueError("model='shadowrate' runs on the Python engine (ccmm_chains_summaries_floor)")
-    smask = np.zeros(N, bool)
-    smask[ndxSHADOWRATE] = True
-    elbdummy = data0[:, ndxSHADOWRATE] <= ELBbound                      # ELBdummy, :131
-    if hybrid and maxlambda:
+    if engine == "native" and not spec.native:
+        raise ValueError(f"model={model!r} runs on the Python engine (ccmm_chains_summaries_floor)")
+    if maxlambda and not spec.maxlambda:
         raise ValueError("goVARhybrid.m computes no max VAR roots (:383-430 commented out)")
     if engine_roots not in ("device", "host"):
         raise ValueError(f"engine_roots must be 'device' or 'host', not {engine_roots!r}")
     if check_stationarity and engine == "native":
         raise ValueError("check_stationarity runs on the Python engine (engine='python'): "
                          "ccmm_batch_config carries no field for it")
-    if check_stationarity and hybrid:
-        import warnings
+    if check_stationarity and not spec.stationarity:
         warnings.warn("no stationarity check for hybrid model")          # mcmcVARhybridGibbs.m:22-24
         check_stationarity = 0
-    dev_roots = maxlambda and engine_roots == "device"
-    K = N * p + 1 + (ndxSHADOWRATE.size * p if hybrid else 0)
+    Ns = ndxSHADOWRATE.size
+    K = N * p + 1 + (Ns * p if spec.ffr_lags else 0)
     costs = [dm.unit_cost(t - p, K, N, n_cens=dm.censored_months(data0, ndxSHADOWRATE, ELBbound, startELB, t)) * C
              for t in Tjumpoffs]
     assignment = dm.lpt_assign(costs, size)
@@ -959,269 +1272,35 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                       model=model) if mine else []
     t_setup = time.perf_counter() - t0
     ctx = context(device)
-    Ns = ndxSHADOWRATE.size
-    chunk = max(1, min(int(chunk), MCMCdraws))
-
-    cumcode = None if cumcode is None else np.asarray(cumcode, bool)
     pct = np.asarray(SET_QUANTILES if setQuantiles is None else setQuantiles, float)
-
-    def run(vidx, attempt):
-        """Run the vintages vidx (indices into `mine`); returns per-vintage results and
-        the list of vintages whose chains were flagged."""
-        us = [units[i] for i in vidx]
-        ids = np.array([(mine[i] * C + c) + attempt * 1_000_003 for i in vidx for c in range(C)],
-                       dtype=np.uint32)
-        # postprocess (and the shadow-rate VAR, whose yhat needs the floored draws): every kept
-        # draw and forecast path stays on the device until the per-vintage summaries
-        # (ccmm_chains_summaries) have been taken
-        dev = postprocess or is_sr
-        hold = dev or bool(Compute_diagnostics)   # the store keeps every kept draw until the end
-        ch, slots, yields = _bh_chain_set(ctx, us, C, seed=rndStream, ids=ids,
-                                          store_capacity=MCMCdraws if hold else chunk,
-                                          gibbsburn=gibbsburn, ELBbound=ELBbound,
-                                          ndxYIELDS=ndxYIELDS, fcstNhorizons=H, Nd=Nd,
-                                          keep_paths=dev, model=model)
-        use_ps = bool(elb_ps and Nproposals and ch.elbTmax and not missing)
-        if missing:
-            ch.set_elb_treatment(missing=True)
-        if use_ps:
-            # block hybrid, shadow rate: m >= MCMCburnin * .5 (:435, mcmcVARshadowrate.m:403);
-            # hybrid: every sweep (mcmcVARhybridGibbs.m:458)
-            ch.set_elb_ps(Nproposals, 1 if hybrid else max(1, -(-burn // 2)))
-            if is_sr:
-                ch.keep_missingrate(True)                  # mcmcVARshadowrate.m:435, 498
-        if check_stationarity:
-            ch.set_stationarity(True)
-        B = ch.B
-        done = 0
-        while done < burn:
-            n = min(chunk, burn - done)
-            ch.sweep(n, store=False)
-            done += n
-            if progress:
-                print(f"[rank {rank}] burn-in {done}/{burn} ({time.perf_counter() - t1:.1f} s)", flush=True)
-        scores = np.empty((Nd, MCMCdraws, 4, B))
-        fYsum = np.zeros((N, H, B))
-        fYcsum = np.zeros((N, H, B))
-        yhsum = np.zeros((N, H, B))
-        Psum = np.zeros((K, N, B))
-        P2sum = np.zeros((K, N, B))
-        elbTmax = ch.elbTmax
-        shadow = np.empty((MCMCdraws, Ns, elbTmax, B)) if elbTmax else None
-        miss = np.empty((MCMCdraws, Ns, elbTmax, B)) if (missing and elbTmax) else None
-        PAIdraws = np.empty((MCMCdraws, K, N, B)) if (keep_draws or (maxlambda and not dev_roots)) else None
-        roots = np.empty((MCMCdraws, B)) if dev_roots else None   # kept draw x chain
-        post, diag = {}, {}
-        done = 0
-        while done < MCMCdraws:
-            n = min(chunk, MCMCdraws - done)
-            ch.sweep(n, store=True)
-            if dev_roots and not hold:  # the chunk's stored draws, before get_draws empties the store
-                for k in range(len(vidx)):
-                    roots[done:done + n, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(n, C)
-            if not hold:
-                fc = ch.get_fcst()
-                if miss is not None:
-                    miss[done:done + n] = ch.get_missingrate()
-                dr = ch.get_draws(which={"PAI_all", "shadowrate_all"})
-                scores[:, done:done + n] = fc["scores"]
-                fYsum += fc["fYsum"]
-                fYcsum += fc["fYcsum"]
-                P = dr["PAI_all"]
-                Psum += P.sum(axis=0)
-                P2sum += (P * P).sum(axis=0)
-                if shadow is not None:
-                    shadow[done:done + n] = dr["shadowrate_all"]
-                if PAIdraws is not None:
-                    PAIdraws[done:done + n] = P
-            done += n
-            if progress:
-                print(f"[rank {rank}] kept {done}/{MCMCdraws} ({time.perf_counter() - t1:.1f} s)", flush=True)
-        if dev:
-            # goVARshadowrateBlockHybrid.m:349-480 on the device, per vintage (data slot)
-            for k, i in enumerate(vidx):
-                thisT, bm, yr = units[i]
-                ycr = np.array(yr, float)
-                if cumcode is not None:
-                    ycr[cumcode] = np.cumsum(ycr[cumcode], axis=1)              # :353
-                if is_sr:
-                    # goVARshadowrate.m:356-495: ydraws = uncensored paths, yields floored; the
-                    # censored paths with the shadow rates floored; shadowratedraws unfloored
-                    q = dict(ycr=ycr, pa=ch.summaries(2, k, pct=pct if postprocess else ()))
-                    q["yd"] = ch.summaries(0, k, realized=yr if postprocess else None,
-                                           pct=pct if postprocess else (), floor_rows=yields, floor=ELBbound)
-                    q["yz"] = ch.summaries(1, k, realized=yr if postprocess else None,
-                                           pct=pct if postprocess else (), floor_rows=smask, floor=ELBbound)
-                    if postprocess:
-                        q["yc"] = ch.summaries(0, k, cumcode=cumcode, realized=ycr, pct=pct, floor_rows=yields,
-                                               floor=ELBbound)
-                        q["sh"] = ch.summaries(0, k, rows=yields, pct=pct)
-                    post[i] = q
-                    continue
-                yd = ch.summaries(1, k, realized=yr, pct=pct)                   # ydraws
-                yc = ch.summaries(1, k, cumcode=cumcode, realized=ycr, pct=pct)  # ycumdraws
-                sh = ch.summaries(0, k, rows=yields, pct=pct)                   # shadowratedraws
-                pa = ch.summaries(2, k, pct=pct)                                # PAI_all
-                post[i] = dict(yd=yd, yc=yc, sh=sh, pa=pa, ycr=ycr)
-                if progress and (k % 8 == 7 or k == len(vidx) - 1):
-                    print(f"[rank {rank}] device summaries {k + 1}/{len(vidx)} vintages "
-                          f"({time.perf_counter() - t1:.1f} s)", flush=True)
-        if hold:
-            if Compute_diagnostics:  # Diagnostics.m on the stored draws, before get_draws empties the store
-                for k, i in enumerate(vidx):
-                    diag[i] = _chain_diagnostics(ch, k)
-            if dev_roots:
-                for k in range(len(vidx)):
-                    roots[:, k * C:(k + 1) * C] = ch.max_var_roots(k).reshape(MCMCdraws, C)
-            fc = ch.get_fcst()
-            scores[:] = fc["scores"]
-            fYsum[:] = fc["fYsum"]
-            fYcsum[:] = fc["fYcsum"]
-            yhsum[:] = fc["yhatsum"]
-            if (is_sr and use_ps) or (missing and elbTmax):
-                miss = ch.get_missingrate()                                     # M x Ns x elbTmax x B
-            need_P = PAIdraws is not None or not dev   # without the device summaries PAImean is taken here
-            dr = ch.get_draws(which={"shadowrate_all"} | ({"PAI_all"} if need_P else set()))
-            if shadow is not None:
-                shadow[:] = dr["shadowrate_all"]
-            if PAIdraws is not None:
-                PAIdraws[:] = dr["PAI_all"]
-            if not dev:
-                Psum += dr["PAI_all"].sum(axis=0)
-                P2sum += (dr["PAI_all"] * dr["PAI_all"]).sum(axis=0)
-        status = ch.get_status()
-        nacc = None
-        if use_ps:
-            psd = ch.get_ps()
-            nacc = psd["countAccept"] + psd["countAcceptBurnin"]
-        ch.close()
-        res, failed = {}, []
-        Ny = int(np.count_nonzero(yields))
-        for k, i in enumerate(vidx):
-            cs = slice(k * C, (k + 1) * C)
-            if np.any(status[cs] & ~_abi.STATUS_INFO):  # bits 1, 64: informational (valid draws)
-                failed.append(i)
-                continue
-            thisT, bm, yr = units[i]
-            nk = MCMCdraws * C
-            r = dict(thisT=thisT, yrealized=yr,
-                     countELBaccept=None if nacc is None else int(nacc[cs].sum()),
-                     logscore=_logmeanexp(scores[:, :, 1, cs].ravel()),
-                     logscoreX=_logmeanexp(scores[:, :, 2, cs].ravel()),
-                     logscoreI=_logmeanexp(scores[:, :, 3, cs].ravel()),
-                     fcstYhat=fYcsum[:, :, cs].sum(axis=2) / (nk * Nd),
-                     fcstShadowYhat=fYsum[ndxYIELDS][:, :, cs].sum(axis=2) / (nk * Nd))
-            if is_sr:
-                q = post[i]
-                RB = yhsum[:, :, cs].sum(axis=2) / nk                          # mcmcVARshadowrate.m:639
-                yh = RB.copy()
-                yh[ndxYIELDS] = q["yd"]["mean"].reshape(N, H, order="F")[ndxYIELDS]   # :683-684
-                r.update(fcstYhat=yh, fcstYhatRB=RB, fcstShadowYhat=RB[ndxYIELDS],
-                         fcstYcensorhat=q["yz"]["mean"].reshape(N, H, order="F"),
-                         PAImean=q["pa"]["mean"].reshape(K, N, order="F"),
-                         PAIstdev=q["pa"]["stdev"].reshape(K, N, order="F"))
-                if postprocess:
-                    nq = pct.size
-                    yc = yh.copy()
-                    if cumcode is not None:
-                        yc[cumcode] = np.cumsum(yc[cumcode], axis=1)
-                    r.update(PAImedian=q["pa"]["median"].reshape(K, N, order="F"),
-                             PAIquantiles=q["pa"]["quantiles"].reshape(K, N, nq, order="F"),
-                             fcstYmedian=q["yd"]["median"].reshape(N, H, order="F"),
-                             fcstYcrps=q["yd"]["crps"].reshape(N, H, order="F"),
-                             fcstYquantiles=q["yd"]["quantiles"].reshape(N, H, nq, order="F"),
-                             fcstYcumrealized=q["ycr"], fcstYcumhat=yc,
-                             fcstYcummedian=q["yc"]["median"].reshape(N, H, order="F"),
-                             fcstYcumcrps=q["yc"]["crps"].reshape(N, H, order="F"),
-                             fcstYcumquantiles=q["yc"]["quantiles"].reshape(N, H, nq, order="F"),
-                             fcstYcensormedian=q["yz"]["median"].reshape(N, H, order="F"),
-                             fcstYcensorcrps=q["yz"]["crps"].reshape(N, H, order="F"),
-                             fcstYcensorquantiles=q["yz"]["quantiles"].reshape(N, H, nq, order="F"),
-                             fcstShadowYmedian=q["sh"]["median"].reshape(Ny, H, order="F"),
-                             fcstShadowYquantiles=q["sh"]["quantiles"].reshape(Ny, H, nq, order="F"),
-                             fcstYmvlogscoreDraws=scores[:, :, 1, cs].ravel(order="F"),
-                             fcstYmvlogscoreXdraws=scores[:, :, 2, cs].ravel(order="F"),
-                             fcstYmvlogscoreIdraws=scores[:, :, 3, cs].ravel(order="F"))
-            elif i in post:
-                q = post[i]
-                nq = pct.size
-                r["PAImean"] = q["pa"]["mean"].reshape(K, N, order="F")
-                r["PAIstdev"] = q["pa"]["stdev"].reshape(K, N, order="F")
-                r["PAImedian"] = q["pa"]["median"].reshape(K, N, order="F")
-                r["PAIquantiles"] = q["pa"]["quantiles"].reshape(K, N, nq, order="F")
-                r["fcstYmedian"] = q["yd"]["median"].reshape(N, H, order="F")
-                r["fcstYcrps"] = q["yd"]["crps"].reshape(N, H, order="F")
-                r["fcstYquantiles"] = q["yd"]["quantiles"].reshape(N, H, nq, order="F")
-                yh = r["fcstYhat"].copy()
-                if cumcode is not None:
-                    yh[cumcode] = np.cumsum(yh[cumcode], axis=1)                # :355
-                r["fcstYcumrealized"] = q["ycr"]
-                r["fcstYcumhat"] = yh
-                r["fcstYcummedian"] = q["yc"]["median"].reshape(N, H, order="F")
-                r["fcstYcumcrps"] = q["yc"]["crps"].reshape(N, H, order="F")
-                r["fcstYcumquantiles"] = q["yc"]["quantiles"].reshape(N, H, nq, order="F")
-                r["fcstShadowYmedian"] = q["sh"]["median"].reshape(Ny, H, order="F")
-                r["fcstShadowYquantiles"] = q["sh"]["quantiles"].reshape(Ny, H, nq, order="F")
-                r["fcstYmvlogscoreDraws"] = scores[:, :, 1, cs].ravel(order="F")
-                r["fcstYmvlogscoreXdraws"] = scores[:, :, 2, cs].ravel(order="F")
-                r["fcstYmvlogscoreIdraws"] = scores[:, :, 3, cs].ravel(order="F")
-            else:
-                r["PAImean"] = Psum[:, :, cs].sum(axis=2) / nk
-                var = P2sum[:, :, cs].sum(axis=2) / nk - r["PAImean"] ** 2
-                r["PAIstdev"] = np.sqrt(np.maximum(var, 0.0))               # std(.,1,1): 1/n
-            if miss is not None and bm.elbT > 0:
-                # missingrate_all permuted to (Nobs, Ns, draws): MATLAB median (NaN if any draw
-                # is NaN) and prctile (NaN draws removed), goVARshadowrate.m:345-348
-                mr = miss[:, :, :bm.elbT, cs].transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
-                r["missingrateMid"] = np.median(mr, axis=2)
-                r["missingrateTails"] = np.moveaxis(matlab_prctile(mr, [5, 25, 75, 95], axis=2), 0, 2)
-            if shadow is not None and keep_draws:
-                r["shadowrate_all"] = shadow[:, :, :bm.elbT, cs].copy()     # M x Ns x elbT x C
-            if shadow is not None:
-                # goVARshadowrateBlockHybrid.m:322-325: DiagnosticsShadowrate per shadow rate over
-                # its months at the ELB, ELBdummy(startELB:thisT, s)
-                r["shadowratePSRF"] = _abi.shadowrate_psrf(shadow[..., cs], elbdummy[startELB - 1:thisT].T)
-                r["shadowratePSRFchains"] = _abi.shadowrate_psrf(shadow[..., cs], elbdummy[startELB - 1:thisT].T,
-                                                                 chains=True)
-            if shadow is not None and bm.elbT > 0:
-                # shadowrate_all permuted to (Nobs, Ns, draws) (:329-334)
-                sr = shadow[:, :, :bm.elbT, cs].transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
-                r["shadowrateMid"] = np.median(sr, axis=2)
-                r["shadowrateTails"] = np.moveaxis(matlab_prctile(sr, [5, 25, 75, 95], axis=2), 0, 2)
-            if PAIdraws is not None:
-                P = PAIdraws[..., cs]
-                if keep_draws:
-                    r["PAI_all"] = P
-                if maxlambda and not dev_roots:
-                    r["drawsMaxVARroot"] = max_var_roots(np.moveaxis(P, 3, 1).reshape(-1, K, N), N, p)
-            if dev_roots:
-                r["drawsMaxVARroot"] = roots[:, cs].ravel()                 # draw slowest, chain fastest
-            for dk, dv in diag.get(i, {}).items():
-                r["diag" + dk[0].upper() + dk[1:]] = dv
-            res[mine[i]] = r
-            if progress and (k % 4 == 3 or k == len(vidx) - 1):
-                print(f"[rank {rank}] results {k + 1}/{len(vidx)} vintages ({time.perf_counter() - t1:.1f} s)",
-                      flush=True)
-        return res, failed
-
-    t1 = time.perf_counter()
+    # postprocess (and the shadow-rate VAR, whose yhat needs the floored draws): every kept draw and forecast
+    # path stays on the device until the per-vintage summaries (ccmm_chains_summaries) have been taken; with
+    # them or Compute_diagnostics the store holds every kept draw until the end of the attempt
+    dev = bool(postprocess or spec.linear_fcst)
+    b = SimpleNamespace(                                 # what the steps of a run share; fixed over the attempts
+        model=model, spec=spec, ctx=ctx, units=units, mine=mine, rank=rank, progress=progress,
+        C=C, N=N, K=K, Ns=Ns, H=H, p=p, Nd=fcstNdraws // MCMCdraws, MCMCdraws=MCMCdraws, burn=burn,
+        chunk=max(1, min(int(chunk), MCMCdraws)), gibbsburn=gibbsburn, ELBbound=ELBbound, rndStream=rndStream,
+        Nproposals=Nproposals, elb_ps=elb_ps, missing=missing, check_stationarity=check_stationarity,
+        postprocess=postprocess, pct=pct, cumcode=None if cumcode is None else np.asarray(cumcode, bool),
+        keep_draws=keep_draws, maxlambda=maxlambda, dev_roots=maxlambda and engine_roots == "device",
+        diagnostics=bool(Compute_diagnostics), dev=dev, hold=dev or bool(Compute_diagnostics),
+        ndxYIELDS=ndxYIELDS, smask=_mask(N, ndxSHADOWRATE), startELB=startELB,
+        elbdummy=data0[:, ndxSHADOWRATE] <= ELBbound,                    # ELBdummy, :131
+        dims=dict(K=K, N=N, H=H, Ny=ndxYIELDS.size, nq=pct.size, Ns=Ns, nd=fcstNdraws * C, nr=MCMCdraws * C),
+        t1=time.perf_counter())
     local, retries = {}, []
     todo = list(range(len(mine)))
     attempt = 0
     if engine == "native":
         if keep_draws or maxlambda:
             raise ValueError("engine='native' keeps no PAI draws (keep_draws / maxlambda)")
-        local, retries = _native_batch(ctx, units, mine, C=C, N=N, p=p, K=K, Ns=Ns, H=H, Nd=Nd,
-                                       MCMCdraws=MCMCdraws, burn=burn, gibbsburn=gibbsburn,
-                                       Nproposals=Nproposals if elb_ps else 0, ELBbound=ELBbound,
-                                       rndStream=rndStream, chunk=chunk, max_retries=max_retries,
-                                       postprocess=postprocess, pct=pct, cumcode=cumcode,
-                                       ndxYIELDS=ndxYIELDS, hybrid=hybrid)
+        local, retries = _native_batch(b, max_retries)
         todo = []
     elif engine != "python":
         raise ValueError(f"engine must be 'python' or 'native', not {engine!r}")
     while todo:
-        res, failed = run(todo, attempt)
+        res, failed = _batch_attempt(b, todo, attempt)
         local.update(res)
         if failed:
             retries.append([mine[i] for i in failed])
@@ -1233,7 +1312,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
             todo = failed
         attempt += 1
     ctx.synchronize()
-    t_run = time.perf_counter() - t1
+    t_run = time.perf_counter() - b.t1
     # ---- end of run: one all-gather of the per-vintage summaries
     allv = dict(local)
     if dist is not None:
@@ -1241,97 +1320,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         dist.all_gather_object(objs, local)
         for d_ in objs:
             allv.update(d_)
-    V = len(Tjumpoffs)
-    Ny = ndxYIELDS.size
-    out = dict(Tjumpoffs=np.array(Tjumpoffs), assignment=assignment,
-               fcstYmvlogscore=np.full(V, np.nan), fcstYmvlogscoreX=np.full(V, np.nan),
-               fcstYmvlogscoreI=np.full(V, np.nan), fcstYhat=np.full((N, H, V), np.nan),
-               fcstShadowYhat=np.full((Ny, H, V), np.nan), fcstYrealized=np.full((N, H, V), np.nan),
-               PAImean=np.full((K, N, V), np.nan), PAIstdev=np.full((K, N, V), np.nan),
-               countELBaccept=np.full(V, -1),
-               shadowratePSRF=np.full((Ns, V), np.nan),                      # :213
-               shadowratePSRFchains=np.full((Ns, V), np.nan),                # psrf across chains (no ref.)
-               shadowrateVintagesMid=np.full((Tdata, Ns, V), np.nan),
-               shadowrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
-    if is_sr:
-        out.update(fcstYhatRB=np.full((N, H, V), np.nan), fcstYcensorhat=np.full((N, H, V), np.nan),
-                   missingrateVintagesMid=np.full((Tdata, Ns, V), np.nan),
-                   missingrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
-    elif missing:
-        out.update(missingrateVintagesMid=np.full((Tdata, Ns, V), np.nan),
-                   missingrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
-    if keep_draws:
-        out["PAI_all"] = {}
-        out["shadowrate_all"] = {}
-    nq = pct.size
-    if postprocess:
-        for nm, shp in (("fcstYmedian", (N, H)), ("fcstYcrps", (N, H)), ("fcstYquantiles", (N, H, nq)),
-                        ("fcstYcumrealized", (N, H)), ("fcstYcumhat", (N, H)), ("fcstYcummedian", (N, H)),
-                        ("fcstYcumcrps", (N, H)), ("fcstYcumquantiles", (N, H, nq)),
-                        ("fcstShadowYmedian", (Ny, H)), ("fcstShadowYquantiles", (Ny, H, nq)),
-                        ("PAImedian", (K, N)), ("PAIquantiles", (K, N, nq)),
-                        ("fcstYmvlogscoreDraws", (fcstNdraws * C,)),
-                        ("fcstYmvlogscoreXdraws", (fcstNdraws * C,)),
-                        ("fcstYmvlogscoreIdraws", (fcstNdraws * C,))):
-            out[nm] = np.full(shp + (V,), np.nan)
-        if is_sr:
-            for nm, shp in (("fcstYcensormedian", (N, H)), ("fcstYcensorcrps", (N, H)),
-                            ("fcstYcensorquantiles", (N, H, nq))):
-                out[nm] = np.full(shp + (V,), np.nan)
-    if maxlambda:
-        out["drawsMaxVARroot"] = np.full((MCMCdraws * C, V), np.nan)
-    if Compute_diagnostics:
-        for dk, shp in zip(DIAG_KEYS, ((N,), (N, 3), (), (3,), (), (3,), (), (3,))):
-            out["diag" + dk[0].upper() + dk[1:]] = np.full(shp + (V,), np.nan)
-    jumpoff = p + elbT0                                                  # :497
-    for v in range(V):
-        r = allv.get(v)
-        if r is None:
-            continue
-        out["fcstYmvlogscore"][v] = r["logscore"]
-        out["fcstYmvlogscoreX"][v] = r["logscoreX"]
-        out["fcstYmvlogscoreI"][v] = r["logscoreI"]
-        out["fcstYhat"][..., v] = r["fcstYhat"]
-        out["fcstShadowYhat"][..., v] = r["fcstShadowYhat"]
-        out["fcstYrealized"][..., v] = r["yrealized"]
-        out["PAImean"][..., v] = r["PAImean"]
-        out["PAIstdev"][..., v] = r["PAIstdev"]
-        if r.get("countELBaccept") is not None:
-            out["countELBaccept"][v] = r["countELBaccept"]
-        if "shadowratePSRF" in r:
-            out["shadowratePSRF"][:, v] = r["shadowratePSRF"]
-        if "shadowratePSRFchains" in r:
-            out["shadowratePSRFchains"][:, v] = r["shadowratePSRFchains"]
-        if "shadowrateMid" in r:
-            thisT = r["thisT"]
-            out["shadowrateVintagesMid"][jumpoff:thisT, :, v] = r["shadowrateMid"]
-            out["shadowrateVintagesTails"][jumpoff:thisT, :, :, v] = r["shadowrateTails"]
-        if "missingrateMid" in r:
-            out["missingrateVintagesMid"][jumpoff:r["thisT"], :, v] = r["missingrateMid"]       # :523-529
-            out["missingrateVintagesTails"][jumpoff:r["thisT"], :, :, v] = r["missingrateTails"]
-        if keep_draws and "PAI_all" in r:
-            out["PAI_all"][v] = r["PAI_all"]
-        if keep_draws and "shadowrate_all" in r:
-            out["shadowrate_all"][v] = r["shadowrate_all"]
-        for nm in ("fcstYmedian", "fcstYcrps", "fcstYquantiles", "fcstYcumrealized", "fcstYcumhat",
-                   "fcstYcummedian", "fcstYcumcrps", "fcstYcumquantiles", "fcstShadowYmedian",
-                   "fcstShadowYquantiles", "PAImedian", "PAIquantiles", "fcstYmvlogscoreDraws",
-                   "fcstYmvlogscoreXdraws", "fcstYmvlogscoreIdraws", "drawsMaxVARroot", "fcstYhatRB",
-                   "fcstYcensorhat", "fcstYcensormedian", "fcstYcensorcrps", "fcstYcensorquantiles",
-                   "diagSVpsrf", "diagSVif", "diagPAIpsrf", "diagPAIif", "diagInvApsrf", "diagInvAif",
-                   "diagPHIpsrf", "diagPHIif"):
-            if nm in r and nm in out:
-                out[nm][..., v] = r[nm]
-    out["fcstYhaterror"] = out["fcstYrealized"] - out["fcstYhat"]                      # :453
-    if is_sr:
-        out["fcstYcensorhaterror"] = out["fcstYrealized"] - out["fcstYcensorhat"]      # goVARshadowrate.m:487
-        if postprocess:
-            out["fcstYcensormederror"] = out["fcstYrealized"] - out["fcstYcensormedian"]  # :488
-    if postprocess:
-        out["fcstYmederror"] = out["fcstYrealized"] - out["fcstYmedian"]              # :454
-        out["fcstYcumhaterror"] = out["fcstYcumrealized"] - out["fcstYcumhat"]        # :463
-        out["fcstYcummederror"] = out["fcstYcumrealized"] - out["fcstYcummedian"]     # :464
-        out["setQuantiles"] = pct
+    out = _batch_out(b, allv, Tjumpoffs, assignment, Tdata, jumpoff=p + elbT0)   # :497
     n_units = len(mine) * C
     out["stats"] = dict(rank=rank, world=size, device=device, vintages_local=len(mine),
                         units_local=n_units, sweeps_local=n_units * (burn + MCMCdraws),
@@ -1339,14 +1328,14 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     return out
 
 
-def _native_batch(ctx, units, mine, *, C, N, p, K, Ns, H, Nd, MCMCdraws, burn, gibbsburn, Nproposals,
-                  ELBbound, rndStream, chunk, max_retries, postprocess, pct, cumcode, ndxYIELDS, hybrid):
+def _native_batch(b, max_retries):
     """The rank's vintage loop through ccmm_run_batch; returns the per-vintage result dicts of
     goVARshadowrateBlockHybrid_batch (keyed by global vintage index) and the retried vintages."""
+    units, mine, spec = b.units, b.mine, b.spec
     if not units:
         return {}, []
-    yields = np.zeros(N, bool)
-    yields[np.asarray(ndxYIELDS, int)] = True
+    yields = _mask(b.N, b.ndxYIELDS)
+    Nproposals = b.Nproposals if b.elb_ps else 0
     vins = []
     for i, (thisT, bm, yr) in enumerate(units):
         m = bm.var
@@ -1355,15 +1344,13 @@ def _native_batch(ctx, units, mine, *, C, N, p, K, Ns, H, Nd, MCMCdraws, burn, g
                          h0vcvsqrt=m.Vol_0vcvsqrt, PAI0=st["PAI"][..., 0], sqrtht0=st["sqrtht"][..., 0], h0init=st["h"][..., 0],
                          elbT0=bm.elbT0, sNaN=bm.sNaN, yrealized=yr, unit=mine[i]))
     bm0 = units[0][1]
-    out = ctx.run_batch(model=_abi.MODEL_HYBRID if hybrid else _abi.MODEL_BLOCKHYBRID, N=N, p=p, Ns=Ns,
-                        ndxS=bm0.ndxS, actual_block=None if hybrid else bm0.actual_block, ndxYields=yields,
-                        nchains=C, MCMCdraws=MCMCdraws, burnin=burn, gibbsburn=gibbsburn, Nproposals=Nproposals,
-                        fcstNdraws=Nd * MCMCdraws, H=H, elb=ELBbound, seed=int(rndStream), chunk=chunk,
-                        max_retries=max_retries, postprocess=postprocess, pct=pct, cumcode=cumcode,
-                        vintages=vins)
+    out = b.ctx.run_batch(model=spec.abi, N=b.N, p=b.p, Ns=b.Ns, ndxS=bm0.ndxS,
+                          actual_block=bm0.actual_block if spec.actual_block else None, ndxYields=yields,
+                          nchains=b.C, MCMCdraws=b.MCMCdraws, burnin=b.burn, gibbsburn=b.gibbsburn,
+                          Nproposals=Nproposals, fcstNdraws=b.Nd * b.MCMCdraws, H=b.H, elb=b.ELBbound,
+                          seed=int(b.rndStream), chunk=b.chunk, max_retries=max_retries,
+                          postprocess=b.postprocess, pct=b.pct, cumcode=b.cumcode, vintages=vins)
     res, retries = {}, []
-    nq = pct.size
-    Ny = int(np.count_nonzero(yields))
     for i, (thisT, bm, yr) in enumerate(units):
         a = int(out["attempts"][i])
         # one list per retry attempt, as the Python engine reports them: vintage i was retried on
@@ -1375,31 +1362,26 @@ def _native_batch(ctx, units, mine, *, C, N, p, K, Ns, H, Nd, MCMCdraws, burn, g
         if a > max_retries + 1:
             res[mine[i]] = None
             continue
-        r = dict(thisT=thisT, yrealized=yr,
-                 countELBaccept=None if Nproposals == 0 else int(out["countELBaccept"][i]),
-                 logscore=out["logscore"][1, i], logscoreX=out["logscore"][2, i], logscoreI=out["logscore"][3, i],
-                 fcstYhat=out["fcstYhat"][..., i].copy(), fcstShadowYhat=out["fcstShadowYhat"][yields][..., i].copy(),
-                 PAImean=out["PAImean"][..., i].copy(), PAIstdev=out["PAIstdev"][..., i].copy())
-        if postprocess:
+        r = dict(thisT=thisT, fcstYrealized=yr, fcstYhat=out["fcstYhat"][..., i].copy(),
+                 fcstShadowYhat=out["fcstShadowYhat"][yields][..., i].copy(),
+                 countELBaccept=None if Nproposals == 0 else int(out["countELBaccept"][i]))
+        if b.postprocess:
             ycr = np.array(yr, float)
             yh = r["fcstYhat"].copy()
-            if cumcode is not None:
-                ycr[cumcode] = np.cumsum(ycr[cumcode], axis=1)
-                yh[cumcode] = np.cumsum(yh[cumcode], axis=1)
-            r.update(PAImedian=out["PAImedian"][..., i], PAIquantiles=out["PAIquantiles"][..., i],
-                     fcstYmedian=out["fcstYmedian"][..., i], fcstYcrps=out["fcstYcrps"][..., i],
-                     fcstYquantiles=out["fcstYquantiles"][..., i], fcstYcumrealized=ycr, fcstYcumhat=yh,
-                     fcstYcummedian=out["fcstYcummedian"][..., i], fcstYcumcrps=out["fcstYcumcrps"][..., i],
-                     fcstYcumquantiles=out["fcstYcumquantiles"][..., i],
-                     fcstShadowYmedian=out["fcstShadowYmedian"][..., i].reshape(Ny, H),
-                     fcstShadowYquantiles=out["fcstShadowYquantiles"][..., i].reshape(Ny, H, nq),
-                     fcstYmvlogscoreDraws=out["scoreDraws"][:, 1, i], fcstYmvlogscoreXdraws=out["scoreDraws"][:, 2, i],
-                     fcstYmvlogscoreIdraws=out["scoreDraws"][:, 3, i])
-        r["shadowratePSRF"] = out["shadowratePSRF"][:, i].copy()          # :322-325
-        r["shadowratePSRFchains"] = out["shadowratePSRFchains"][:, i].copy()
+            if b.cumcode is not None:
+                ycr[b.cumcode] = np.cumsum(ycr[b.cumcode], axis=1)
+                yh[b.cumcode] = np.cumsum(yh[b.cumcode], axis=1)
+            r.update(fcstYcumrealized=ycr, fcstYcumhat=yh)
+        for f in _fields(b.postprocess, False, False):
+            if f.src == "logscore":
+                r[f.name] = out["logscore"][f.stat, i]
+            elif f.src == "scores":
+                r[f.name] = out["scoreDraws"][:, f.stat, i]
+            elif f.name not in r:                                           # :322-325 and the device summaries
+                r[f.name] = out[f.name][..., i].copy()
         if bm.elbT > 0:
             sh = out["shadowrate_all"][:, :, :bm.elbT, :, i]                 # M x Ns x elbT x C
-            sr = sh.transpose(2, 1, 0, 3).reshape(bm.elbT, Ns, -1)
+            sr = sh.transpose(2, 1, 0, 3).reshape(bm.elbT, b.Ns, -1)
             r["shadowrateMid"] = np.median(sr, axis=2)
             r["shadowrateTails"] = np.moveaxis(matlab_prctile(sr, [5, 25, 75, 95], axis=2), 0, 2)
         res[mine[i]] = r
@@ -1407,7 +1389,7 @@ def _native_batch(ctx, units, mine, *, C, N, p, K, Ns, H, Nd, MCMCdraws, burn, g
 
 
 def goVARshadowrate_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean, *,
-                          Nproposals=100, **kw):
+                          Nproposals=_MODELS["shadowrate"].Nproposals, **kw):
     """goVARshadowrate.m (the quasi-real-time OOS run of the shadow-rate VAR, mcmcVARshadowrate per
     vintage, parfor at :265, elb.Nproposals = 100 at mcmcVARshadowrate.m:169, modellabel
     ELBsampling) as one device-resident chain set per rank; arguments and outputs of

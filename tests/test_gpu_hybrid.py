@@ -147,7 +147,8 @@ def test_lag_twin_bit_identical(pkg, ctx, oracle, hy, fred):
         ch.set_state(*[np.stack([s[k] for s in sts], -1) for k in ("PAI", "A", "sqrtht", "h", "sqrtPHI")])
         ch.sweep(3, store=True)
         out[lx] = (ch.get_state(), ch.get_shadowrate(), ch.get_status())
-    assert np.all(out[1][2] & ~1 == 0) and np.all(out[0][2] & ~1 == 0)
+    info = pkg._abi.STATUS_INFO                      # bits 1, 64: informational (valid draws)
+    assert np.all(out[1][2] & ~info == 0) and np.all(out[0][2] & ~info == 0)
     for k in out[1][0]:
         np.testing.assert_array_equal(out[1][0][k], out[0][0][k], err_msg=k)
     np.testing.assert_array_equal(out[1][1], out[0][1])
