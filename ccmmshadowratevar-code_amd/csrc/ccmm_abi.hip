@@ -258,8 +258,7 @@ int ccmm_selftest_mfma_f64(ccmm_ctx* ctx, const double* A16x4, const double* B4x
     dd.alloc(256);
     HIPCHECK(hipMemcpy(a.p, A16x4, 64 * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(b.p, B4x16, 64 * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mfma_selftest, dim3(1), dim3(64), 0, ctx->stream, a.p, b.p, dd.p);
-    HIPCHECK(hipGetLastError());
+    HIPCHECK(launch_mfma_selftest(ctx->stream, a.p, b.p, dd.p));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(D16x16, dd.p, 256 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
@@ -279,8 +278,7 @@ int ccmm_selftest_mfma_f64_acc(ccmm_ctx* ctx, int nprobe, const double* A16x4, c
     HIPCHECK(hipMemcpy(a.p, A16x4, (size_t)64 * nprobe * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(b.p, B4x16, (size_t)64 * nprobe * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(cc.p, C16x16, (size_t)256 * nprobe * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mfma_selftest_acc, dim3(nprobe), dim3(64), 0, ctx->stream, a.p, b.p, cc.p, dd.p, nprobe);
-    HIPCHECK(hipGetLastError());
+    HIPCHECK(launch_mfma_selftest_acc(ctx->stream, a.p, b.p, cc.p, dd.p, nprobe));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(D16x16, dd.p, (size_t)256 * nprobe * sizeof(double), hipMemcpyDeviceToHost));
     return 0;

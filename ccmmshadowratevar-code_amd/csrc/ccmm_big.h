@@ -28,7 +28,7 @@ inline size_t big_stage_lds_doubles(const Dims& d, int ncol) {
 // The solve's choice between three branches: the twin (ncol columns) staged in LDS; a twin read from L2 because
 // KP > kStageMaxKP (the kernel keeps kStageMaxKP / 64 column sums per wave); a twin read from L2 because the staged
 // size exceeds one CU's LDS.  Without a twin the kernel reads X itself.  A shape whose unstaged size alone exceeds
-// kLdsCu is not refused here: hipFuncSetAttribute fails in big_launch_cta and the error is returned.
+// kLdsCu is not refused here: raising the LDS limit fails in big_launch_solve and the error is returned.
 struct BigSolvePlan {
   bool staged;
   size_t lds;
@@ -53,12 +53,16 @@ struct ColX {
   int ncol;  // columns per twin (data, actual rates, ones, zeros)
 };
 
-// groups: ngroups x int4 systems (c*N + j) sharing one design X slab (-1 padded);
-// phase_mask: 1 Gram, 2 Cholesky, 4 solve.  Ubuf: B x N x TP scratch (U = E A');
-// Dinv: nmat x (KP/64) x 64 x 64 inverses of the Cholesky factor's diagonal blocks.
-hipError_t big_launch_cta(hipStream_t st, const Dims& d, const int* Tslot, const int* slotIV,
-                          const double* iVdiag, const double* iVb, XSel xs, ChainState cs,
-                          const int4* groups, int ngroups, double* rdiag, RngArgs ra, double* Ubuf,
-                          double* Dinv, int phase_mask, ColX cx);
+// the three phases of the large CTA, in stream order.  CCMM_BIG_MASK (ablation build, timing only) drops phases
+constexpr int kBigGram = 1, kBigChol = 2, kBigSolve = 4, kBigAll = kBigGram | kBigChol | kBigSolve;
+// groups: ngroups x int4 systems (c*N + j) sharing one design X slab (-1 padded)
+hipError_t big_launch_gram(hipStream_t st, const Dims& d, const int* Tslot, XSel xs, ChainState cs, const int4* groups,
+                           int ngroups, ColX cx);
+// Dinv: nmat x (KP/64) x 64 x 64 inverses of the Cholesky factor's diagonal blocks
+hipError_t big_launch_chol(hipStream_t st, const Dims& d, const int* slotIV, const double* iVdiag, ChainState cs,
+                           double* rdiag, double* Dinv);
+// Ubuf: B x N x TP scratch (U = E A')
+hipError_t big_launch_solve(hipStream_t st, const Dims& d, const int* Tslot, const double* iVb, XSel xs, ChainState cs,
+                            const double* rdiag, RngArgs ra, double* Ubuf, const double* Dinv, ColX cx);
 
 }  // namespace ccmm

@@ -869,33 +869,27 @@ __global__ __launch_bounds__(1024) void k_cta_solve_big(Dims d, const int* __res
 }
 
 // ============================================================== host launchers
-hipError_t big_launch_cta(hipStream_t st, const Dims& d, const int* Tslot, const int* slotIV,
-                          const double* iVdiag, const double* iVb, XSel xs, ChainState cs,
-                          const int4* groups, int ngroups, double* rdiag, RngArgs ra, double* Ubuf,
-                          double* Dinv, int phase_mask, ColX cx) {
-  static const int skip = env_ablation("CCMM_SOLVE_SKIP", 0);
-  static const int cskip = env_ablation("CCMM_CHOL_SKIP", 0);
+// one workgroup per (lower 64 x 64 tile, group of systems sharing a design)
+hipError_t big_launch_gram(hipStream_t st, const Dims& d, const int* Tslot, XSel xs, ChainState cs, const int4* groups,
+                           int ngroups, ColX cx) {
   const int nt = d.KP / kBT;
-  if (phase_mask & 1)
-    hipLaunchKernelGGL(k_gram_big, dim3(nt * (nt + 1) / 2, ngroups), dim3(256), 0, st, d, Tslot, xs, cs,
-                       groups, cx);
-  if (phase_mask & 2)
-    hipLaunchKernelGGL(k_chol_big, dim3(d.nmat), dim3(256), 0, st, d, slotIV, iVdiag, cs, rdiag, Dinv,
-                       cskip);
-  if (phase_mask & 4) {
-    // the staged twin when the design fits kStageMaxKP and its LDS fits beside the rest
-    // (big_solve_plan)
-    ColX cs_x = cx;
-    const BigSolvePlan pl = big_solve_plan(d, cx.pool != nullptr, cx.ncol);
-    if (!pl.staged) cs_x.ncol = 0;
-    const size_t lds = pl.lds;
-    hipError_t e = hipFuncSetAttribute((const void*)k_cta_solve_big,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_cta_solve_big, dim3(d.B), dim3(1024), lds, st, d, Tslot, iVb, xs, cs, rdiag,
-                       ra, Ubuf, Dinv, skip, cs_x);
-  }
-  return hipGetLastError();
+  return launch_k(k_gram_big, dim3(nt * (nt + 1) / 2, ngroups), dim3(256), 0, false, st, d, Tslot, xs, cs, groups, cx);
+}
+
+hipError_t big_launch_chol(hipStream_t st, const Dims& d, const int* slotIV, const double* iVdiag, ChainState cs,
+                           double* rdiag, double* Dinv) {
+  static const int cskip = env_ablation("CCMM_CHOL_SKIP", 0);
+  return launch_k(k_chol_big, dim3(d.nmat), dim3(256), 0, false, st, d, slotIV, iVdiag, cs, rdiag, Dinv, cskip);
+}
+
+hipError_t big_launch_solve(hipStream_t st, const Dims& d, const int* Tslot, const double* iVb, XSel xs, ChainState cs,
+                            const double* rdiag, RngArgs ra, double* Ubuf, const double* Dinv, ColX cx) {
+  static const int skip = env_ablation("CCMM_SOLVE_SKIP", 0);
+  // the staged twin when the design fits kStageMaxKP and its LDS fits beside the rest (big_solve_plan)
+  const BigSolvePlan pl = big_solve_plan(d, cx.pool != nullptr, cx.ncol);
+  if (!pl.staged) cx.ncol = 0;
+  return launch_k(k_cta_solve_big, dim3(d.B), dim3(1024), pl.lds, true, st, d, Tslot, iVb, xs, cs, rdiag, ra, Ubuf, Dinv,
+                  skip, cx);
 }
 
 }  // namespace ccmm

@@ -934,41 +934,26 @@ hipError_t bign_launch_astep(hipStream_t st, const Dims& d, const int* Tslot, Ch
   const int NPAD = bign_astep_npad(d);
   const int nt = NPAD / 64;
   const int ngr = (d.N - 1 + 3) / 4;
-  hipLaunchKernelGGL(k_astep_gram, dim3(nt * (nt + 1) / 2, d.B * ngr), dim3(256), 0, st, d, Tslot, cs, gbuf, NPAD);
-  const size_t lds = bign_astep_lds();
-  hipError_t e = hipFuncSetAttribute((const void*)k_astep_big, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
+  hipError_t e = launch_k(k_astep_gram, dim3(nt * (nt + 1) / 2, d.B * ngr), dim3(256), 0, false, st, d, Tslot, cs, gbuf,
+                          NPAD);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_astep_big, dim3(d.N - 1, d.B), dim3(256), lds, st, d, Tslot, cs, ra, gbuf, NPAD);
-  const size_t lds2 = bign_astep_fin_lds(d.N);
-  e = hipFuncSetAttribute((const void*)k_astep_fin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+  e = launch_k(k_astep_big, dim3(d.N - 1, d.B), dim3(256), bign_astep_lds(), true, st, d, Tslot, cs, ra, gbuf, NPAD);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_astep_fin, dim3(d.B), dim3(256), lds2, st, d, Tslot, cs, logy2offset);
-  return hipGetLastError();
+  return launch_k(k_astep_fin, dim3(d.B), dim3(256), bign_astep_fin_lds(d.N), true, st, d, Tslot, cs, logy2offset);
 }
 
 hipError_t bign_launch_phi(hipStream_t st, const Dims& d, const int* Tslot, int dPHI, const double* sPHI,
                            ChainState cs, double* scr) {
-  const size_t lds = bign_phi_lds();
-  hipError_t e = hipFuncSetAttribute((const void*)k_phi_big, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_phi_big, dim3(d.B), dim3(1024), lds, st, d, Tslot, dPHI, sPHI, cs, scr);
-  return hipGetLastError();
+  return launch_k(k_phi_big, dim3(d.B), dim3(1024), bign_phi_lds(), true, st, d, Tslot, dPHI, sPHI, cs, scr);
 }
 
 hipError_t bign_launch_sv(hipStream_t st, const Dims& d, const int* Tslot, const double* V0inv,
                           const double* V0invm, ChainState cs, RngArgs ra, double* scr) {
-  const size_t lds = bign_sv_lds(d.N);
-  hipError_t e = hipFuncSetAttribute((const void*)k_sv_big, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return e;
   // CCMM_SV_SKIP: timing ablation of k_sv_big phases (1 M_t, 2 M_t'M_t, 4 Cholesky + inverse,
   // 8 forward product, 16 backward pass, 32 Linv_t store); results are wrong when set
   static const int skip = env_ablation("CCMM_SV_SKIP", 0);
-  hipLaunchKernelGGL(k_sv_big, dim3(d.B), dim3(kSvNT), lds, st, d, Tslot, V0inv, V0invm, cs, ra, scr,
-                     bign_sv_scratch(d), skip);
-  return hipGetLastError();
+  return launch_k(k_sv_big, dim3(d.B), dim3(kSvNT), bign_sv_lds(d.N), true, st, d, Tslot, V0inv, V0invm, cs, ra, scr,
+                  bign_sv_scratch(d), skip);
 }
 
 }  // namespace ccmm

@@ -43,9 +43,9 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   bool aswitch = false;
   DBuf<double> AelbD;
   DBuf<uint8_t> atELBD;
-  // timing-only ablation of k_gram_chol (results invalid): 1 = no SYRK, 2 = no Cholesky
+  // timing-only ablation of k_gram_chol (results invalid): the kGc* bits of ccmm_sweep.h
   int gc_mode = ccmm::env_ablation("CCMM_GC_MODE", 0);
-  // phase skips (timing only) and bit 128 (full-row block factors, same draws): ablation build only
+  // the kSv* bits of ccmm_svpart.h (phase skips, timing-only bits, kSvFullRows): ablation build only
   int sv_mode = ccmm::env_ablation("CCMM_SV_MODE", 0);
   int mfma_lock = 0;  // MFMA phase lock id (ccmm_chains_set_mfma_lock) and the set's event in it
   hipEvent_t mfma_ev = nullptr;
@@ -85,7 +85,7 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   int nGroups = 0;
   DBuf<int4> bigGroups;
   DBuf<double> Ubuf, Dinv, bigW, bigScr;
-  int big_mask = ccmm::env_ablation("CCMM_BIG_MASK", 7);
+  int big_mask = ccmm::env_ablation("CCMM_BIG_MASK", ccmm::kBigAll);
 
   // ---------------------------------------------------------------- ELB model
   // block-hybrid ELB model (mcmcVARshadowrateBlockHybrid.m): X/Y slabs 0..ndata-1 hold
@@ -109,7 +109,7 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   int elb_Afull = 0;                 // ccmm_gibbs_shadowrates*: A = inverse of a general impact matrix
   uint8_t* elb_flags = nullptr;      // drawTruncNormal branch flags of the last ELB step (or nullptr)
   DBuf<uint8_t> dElbFlags;
-  // timing-only ablation of k_elb_gibbs (results invalid): 1 no truncnorm, 2 no uniforms
+  // timing-only ablation of the ELB Gibbs kernels (results invalid): the kElb* bits of ccmm_elb.h
   int elb_mode = ccmm::env_ablation("CCMM_ELB_MODE", 0);
   DBuf<double> elbXch;  // k_elb_gibbs_mp exchange between a chain's parts, tagged by elb_epoch
   const double* elbXchZeroed = nullptr;
@@ -269,8 +269,6 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   void run_weights(const ccmm::ChainState& cs, int sqrt_form);
   void run_cta(const ccmm::RngArgs& ra);
   void run_astep_big(const ccmm::RngArgs& ra);
-  void run_sv_big(const ccmm::RngArgs& ra);
-  void run_phi_big(const ccmm::RngArgs& ra);
   void run_cta_big(const ccmm::RngArgs& ra, const ccmm::ChainState& cs);
   bool solve_split_ok();
   void run_cta_lag(const ccmm::RngArgs& ra, const ccmm::ChainState& cs);

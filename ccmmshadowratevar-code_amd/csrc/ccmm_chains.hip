@@ -444,7 +444,7 @@ void ccmm_chains::export_lag_gram(const char* inactive, int mode) {
 // Parity export: the lag path's weighted Gram of every (chain, equation) system at the current
 // state, [c b'; b M] (K x K, without the prior), decoded from the kernel's tile slots
 void ccmm_chains::export_cta_gram(double* out) {
-  export_lag_gram("ccmm_chains_get_cta_gram: the lag-structured CTA path is not active", 8);
+  export_lag_gram("ccmm_chains_get_cta_gram: the lag-structured CTA path is not active", kLagGramExport);
   const int NT = lagNT, NTILE = gl_ntile(NT), K = d.K, KL = K - 1;
   std::vector<double> o((size_t)gl_out_len(NT));
   for (int mat = 0; mat < d.nmat; ++mat) {
@@ -774,10 +774,8 @@ int ccmm_chains_pai_moments(ccmm_chains* ch, int reset, double* sum, double* sum
     }
     require(ch->stored >= ch->mom_done, "ccmm_chains_pai_moments: the store was reset; call with reset != 0");
     if (ch->stored > ch->mom_done && ch->sPAI.p) {
-      hipLaunchKernelGGL(k_pai_moments, dim3((unsigned)((B * per + 255) / 256)), dim3(256), 0, ch->ctx->stream,
-                         ch->sPAI.p, ch->cfg.store_capacity, ch->mom_done, ch->stored, (int)per, (int)B,
-                         ch->paiMom.p, ch->paiMom.p + B * per);
-      HIPCHECK(hipGetLastError());
+      HIPCHECK(launch_pai_moments(ch->ctx->stream, ch->sPAI.p, ch->cfg.store_capacity, ch->mom_done, ch->stored,
+                                  (int)per, (int)B, ch->paiMom.p, ch->paiMom.p + B * per));
       ch->mom_done = ch->stored;
     }
     if (sum || sumsq) {

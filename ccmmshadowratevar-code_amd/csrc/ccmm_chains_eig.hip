@@ -47,23 +47,6 @@ void max_var_root_device_src(ccmm_ctx* ctx, int M, int N, int p, const EigSrc& s
   if (info) std::memcpy(info, fl.data(), (size_t)M * sizeof(int));
 }
 
-namespace {
-
-// accepted chains (acc[c] != 0) take PAI, E and the status word back from the snapshot
-__global__ __launch_bounds__(256) void k_stat_select(int nPAI, int nE, const int* __restrict__ acc,
-                                                     const double* __restrict__ sPAI, const double* __restrict__ sE,
-                                                     const int* __restrict__ sStatus, double* __restrict__ PAI,
-                                                     double* __restrict__ E, int* __restrict__ status) {
-  const int c = blockIdx.y;
-  if (!acc[c]) return;
-  const size_t oP = (size_t)c * nPAI, oE = (size_t)c * nE;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nPAI; i += gridDim.x * blockDim.x) PAI[oP + i] = sPAI[oP + i];
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nE; i += gridDim.x * blockDim.x) E[oE + i] = sE[oE + i];
-  if (blockIdx.x == 0 && threadIdx.x == 0) status[c] = sStatus[c];
-}
-
-}  // namespace
-
 // After the coefficient block of a sweep (run_cta + cta_fallback with attempt 0).  One synchronisation per
 // root evaluation; the CTA kernels are launched exactly as in a sweep, for the whole set.
 void ccmm_chains::run_stationarity(const RngArgs& ra0) {
@@ -125,8 +108,8 @@ void ccmm_chains::run_stationarity(const RngArgs& ra0) {
     run_cta(ra);
     cta_fallback(ra);
     launch(KID_STATSEL, [&] {
-      hipLaunchKernelGGL(k_stat_select, dim3(8, B), dim3(256), 0, ctx->stream, nPAI, nE, statAcc.p, statPAI.p,
-                         statE.p, statStatus.p, PAI.p, E.p, status.p);
+      HIPCHECK(eig_launch_stat_select(ctx->stream, B, nPAI, nE, statAcc.p, statPAI.p, statE.p, statStatus.p, PAI.p, E.p,
+                                      status.p));
     });
     open = evaluate();
   }

@@ -345,17 +345,14 @@ void ccmm_chains::run_elb(const RngArgs& ra, bool kept) {
     HIPCHECK(hipEventRecord(specEv.join, aux2));
     HIPCHECK(hipStreamWaitEvent(ctx->stream, specEv.join, 0));
     ep.spec = 1;  // (ep.psFlag: set by run_ps)
-    hipLaunchKernelGGL(k_elb_spec_select, dim3(d.B), dim3(256), 0, ctx->stream, ep, slot.p, d.B);
-    HIPCHECK(hipGetLastError());
+    HIPCHECK(launch_elb_spec_select(ctx->stream, ep, slot.p, d.B));
   }
   // the alternate draw (:470-475): this sweep's precision and linear term (the condition records above,
   // which hold the observed data only), into the missingrate buffer alone
   if (elb_alt) run_draw1(ra, e, 2, !opt[OPT_PS_CHOL_LDS]);
-  const int nrb = e.elbTmax * Ns * (p + 1);
   launch(KID_ELBREBUILD, [&] {
-    hipLaunchKernelGGL(k_elb_rebuild, dim3((nrb + 255) / 256, d.B), dim3(256), 0, ctx->stream, d, e,
-                       xsel(), cs, cfg.ndata, lag_capable ? Dpool.p : nullptr, ldd, drows,
-                       colx_capable ? Dcpool.p : nullptr, dcld, (long long)dcslab);
+    HIPCHECK(launch_elb_rebuild(ctx->stream, d, e, xsel(), cs, cfg.ndata, lag_capable ? Dpool.p : nullptr, ldd, drows,
+                                colx_capable ? Dcpool.p : nullptr, dcld, (long long)dcslab));
   });
   resid_valid = false;  // X, Y changed: RESID is recomputed before the next CTA
 }

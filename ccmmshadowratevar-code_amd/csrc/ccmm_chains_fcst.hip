@@ -107,17 +107,13 @@ void ccmm_chains::run_fcst(const RngArgs& ra) {
   a.seed = cfg.seed; a.sweep = ra.sweep; a.ids = ra.ids;
   a.fY = fY.p; a.fYc = fYc.p; a.yhat = fYhat.p; a.scores = fSc.p; a.status = fStatus.p;
   a.gl = gl_nodes();
-  a.mode = env_ablation("CCMM_FCST_MODE", 0);  // timing-only: 1 no scores, 2 no horizons
+  a.mode = env_ablation("CCMM_FCST_MODE", 0);  // timing-only (kFcstNoScores, kFcstNoHorizons)
   const XSel xs = xsel();
   launch(KID_FCST, [&] {
-    hipLaunchKernelGGL(k_fcst_jumpoff, dim3(B), dim3(256), 0, fst, N, cfg.p, N * cfg.p + 1, d.TP,
-                       Tslot.p, slot.p, xs.ypool, xs.yidx, fldXj, fXj.p, hybrid ? cfg.Ns : 0,
-                       hybrid ? dNdxS.p : nullptr, cfg.elb);
+    HIPCHECK(launch_fcst_jumpoff(fst, a, d.TP, Tslot.p, xs.ypool, xs.yidx, fXj.p));
     HIPCHECK(launch_fcst(fst, a, fSv1.p, opt[OPT_FCST_REG] != 0));
-    hipLaunchKernelGGL(k_fcst_accum, dim3(B), dim3(256), 0, fst, N, H, Nd,
-                       cfg.store_capacity, fstored, fY.p, fYc.p, (fcst_bh || hybrid) ? nullptr : fYhat.p, fSc.p,
-                       fYsum.p, fYcsum.p, fYhatsum.p, fScStore.p, fKeep ? fPaths.p : nullptr,
-                       fKeep ? fPathsC.p : nullptr);
+    HIPCHECK(launch_fcst_accum(fst, a, cfg.store_capacity, fstored, (fcst_bh || hybrid) ? nullptr : fYhat.p, fYsum.p,
+                               fYcsum.p, fYhatsum.p, fScStore.p, fKeep ? fPaths.p : nullptr, fKeep ? fPathsC.p : nullptr));
   }, fst);
   ++fstored;
   if (overlap) {

@@ -75,29 +75,6 @@ void ccmm_chains::run_astep_big(const RngArgs& ra) {
     HIPCHECK(bign_launch_astep(ctx->stream, d, Tslot.p, cs, ra, cfg.logy2offset, bigW.p));
   });
 }
-void ccmm_chains::run_sv_big(const RngArgs& ra) {
-  bigScr.alloc((size_t)d.B * bign_sv_scratch(d));
-  ChainState cs = view();
-  launch(KID_SVMIX, [&] {
-    hipLaunchKernelGGL(k_sv_mix, dim3((d.N * d.TP + 255) / 256, d.B), dim3(256), 0, ctx->stream,
-                       d, Tslot.p, cs, ra);
-  });
-  launch(KID_SVBIG, [&] {
-    HIPCHECK(bign_launch_sv(ctx->stream, d, Tslot.p, V0inv.p, V0invm.p, cs, ra, bigScr.p));
-  });
-}
-void ccmm_chains::run_phi_big(const RngArgs& ra) {
-  Zphi.alloc((size_t)d.B * d.N * (d.TP + cfg.dPHI));
-  bigScr.alloc((size_t)d.B * bign_sv_scratch(d));  // >= 3 N^2 per chain
-  ChainState cs = view();
-  launch(KID_PHIGEN, [&] {
-    hipLaunchKernelGGL(k_phi_gen, dim3((d.N * (d.TP + cfg.dPHI) + 255) / 256, d.B), dim3(256), 0,
-                       ctx->stream, d, Tslot.p, cfg.dPHI, cs, ra);
-  });
-  launch(KID_PHIBIG, [&] {
-    HIPCHECK(bign_launch_phi(ctx->stream, d, Tslot.p, cfg.dPHI, sPHI.p, cs, bigScr.p));
-  });
-}
 
 // CTA for large systems (ccmm_big.hip): weights -> multi-equation MFMA Gram -> per-system
 // blocked Cholesky -> per-chain sequential solve
@@ -106,19 +83,19 @@ void ccmm_chains::run_cta_big(const RngArgs& ra, const ChainState& cs) {
   Dinv.alloc((size_t)d.nmat * d.KP * 64);
   PhaseScope phase(ctx->device, mfma_lock, ctx->stream, mfma_ev);
   run_weights(cs, 0);
+  // (a phase CCMM_BIG_MASK drops still records its event pair)
   launch(KID_GRAMBIG, [&] {
-    HIPCHECK(big_launch_cta(ctx->stream, d, Tslot.p, slot.p, iVdiag.p, iVb.p, xsel(), cs, bigGroups.p,
-                            nGroups, rdiag.p, ra, Ubuf.p, Dinv.p, 1 & big_mask, colx()));
+    if (big_mask & kBigGram)
+      HIPCHECK(big_launch_gram(ctx->stream, d, Tslot.p, xsel(), cs, bigGroups.p, nGroups, colx()));
   });
   launch(KID_CHOLBIG, [&] {
-    HIPCHECK(big_launch_cta(ctx->stream, d, Tslot.p, slot.p, iVdiag.p, iVb.p, xsel(), cs, bigGroups.p,
-                            nGroups, rdiag.p, ra, Ubuf.p, Dinv.p, 2 & big_mask, colx()));
+    if (big_mask & kBigChol) HIPCHECK(big_launch_chol(ctx->stream, d, slot.p, iVdiag.p, cs, rdiag.p, Dinv.p));
   });
   phase.release();
   join_fcst();  // the previous kept sweep's predictive density reads PAI
   launch(KID_SOLVEBIG, [&] {
-    HIPCHECK(big_launch_cta(ctx->stream, d, Tslot.p, slot.p, iVdiag.p, iVb.p, xsel(), cs, bigGroups.p,
-                            nGroups, rdiag.p, ra, Ubuf.p, Dinv.p, 4 & big_mask, colx()));
+    if (big_mask & kBigSolve)
+      HIPCHECK(big_launch_solve(ctx->stream, d, Tslot.p, iVb.p, xsel(), cs, rdiag.p, ra, Ubuf.p, Dinv.p, colx()));
   });
 }
 
@@ -194,36 +171,38 @@ void ccmm_chains::ensure_sv() {
   svG.alloc((size_t)2 * d.B * (d.TP + 1) * NN);  // fill vectors g | SV normals z
 }
 
+// KSC indicators, then the partitioned sampler (N <= 32) or the large-N sampler (ccmm_bign.hip)
 void ccmm_chains::run_sv(const RngArgs& ra) {
-  if (d.N > kMaxNSmall) {
-    run_sv_big(ra);
-    return;
-  }
-  ensure_sv();
+  const bool bign = d.N > kMaxNSmall;
+  if (bign)
+    bigScr.alloc((size_t)d.B * bign_sv_scratch(d));
+  else
+    ensure_sv();
   ChainState cs = view();
-  launch(KID_SVMIX, [&] {
-    hipLaunchKernelGGL(k_sv_mix, dim3((d.N * d.TP + 255) / 256, d.B), dim3(256), 0, ctx->stream,
-                       d, Tslot.p, cs, ra);
-  });
-  launch(KID_SVSAMPLE, [&] {
-    HIPCHECK(sv_launch_part(d.N, ctx->stream, d, Tslot.p, V0inv.p, V0invm.p, cs, ra, svSep.p, svG.p, sv_mode,
+  launch(KID_SVMIX, [&] { HIPCHECK(launch_sv_mix(ctx->stream, d, Tslot.p, cs, ra)); });
+  if (bign)
+    launch(KID_SVBIG, [&] {
+      HIPCHECK(bign_launch_sv(ctx->stream, d, Tslot.p, V0inv.p, V0invm.p, cs, ra, bigScr.p));
+    });
+  else
+    launch(KID_SVSAMPLE, [&] {
+      HIPCHECK(sv_launch_part(d.N, ctx->stream, d, Tslot.p, V0inv.p, V0invm.p, cs, ra, svSep.p, svG.p, sv_mode,
                               opt[OPT_SV_NWG], opt[OPT_SV_MFMA] != 0));
-  });
+    });
 }
 
+// the inverse-Wishart normals, then k_phi (N <= 32) or k_phi_big (always in stream order: sweep_once forks N <= 32 only)
 void ccmm_chains::run_phi(const RngArgs& ra, hipStream_t on) {
-  if (d.N > kMaxNSmall) {
-    run_phi_big(ra);
-    return;
-  }
+  const bool bign = d.N > kMaxNSmall;
   hipStream_t st = on ? on : ctx->stream;
   Zphi.alloc((size_t)d.B * d.N * (d.TP + cfg.dPHI));
+  if (bign) bigScr.alloc((size_t)d.B * bign_sv_scratch(d));  // >= 3 N^2 per chain
   ChainState cs = view();
-  launch(KID_PHIGEN, [&] {
-    hipLaunchKernelGGL(k_phi_gen, dim3((d.N * (d.TP + cfg.dPHI) + 255) / 256, d.B), dim3(256), 0,
-                       st, d, Tslot.p, cfg.dPHI, cs, ra);
-  }, st);
-  launch(KID_PHI, [&] { HIPCHECK(launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs)); }, st);
+  launch(KID_PHIGEN, [&] { HIPCHECK(launch_phi_gen(st, d, Tslot.p, cfg.dPHI, cs, ra)); }, st);
+  if (bign)
+    launch(KID_PHIBIG, [&] { HIPCHECK(bign_launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs, bigScr.p)); }, st);
+  else
+    launch(KID_PHI, [&] { HIPCHECK(launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs)); }, st);
 }
 
 void ccmm_chains::run_store() {
@@ -236,35 +215,31 @@ void ccmm_chains::run_store() {
   sSqrtht.alloc(B * cap * (size_t)cfg.T * N);
   Store st{sPAI.p, sPHI_.p, sInvA.p, sSqrtht.p, cfg.store_capacity, stored, cfg.T};
   ChainState cs = view();
-  launch(KID_STORE, [&] {
-    hipLaunchKernelGGL(k_store, dim3(64, d.B), dim3(256), 0, ctx->stream, d, cs, st);
-  });
+  launch(KID_STORE, [&] { HIPCHECK(launch_store(ctx->stream, d, cs, st)); });
   if (bh && cfg.elbTmax > 0) {
     sShadow.alloc(B * cap * cfg.Ns * cfg.elbTmax);
     ElbDev e = elb_view();
     launch(KID_STORE, [&] {
       if (elb_missing)  // shadowrate = NaN (:492; mcmcVARshadowrate.m:448)
-        hipLaunchKernelGGL(k_ps_first_store, dim3(d.B), dim3(256), 0, ctx->stream, (const double*)nullptr, e.elbT,
-                           cs.slot, sShadow.p, cfg.Ns * cfg.elbTmax, cfg.Ns, cfg.store_capacity, stored);
+        HIPCHECK(launch_ps_first_store(ctx->stream, d.B, nullptr, e.elbT, cs.slot, sShadow.p, cfg.Ns * cfg.elbTmax,
+                                       cfg.Ns, cfg.store_capacity, stored));
       else
-        hipLaunchKernelGGL(k_elb_store, dim3(d.B), dim3(256), 0, ctx->stream, e, cs, sShadow.p,
-                           cfg.store_capacity, stored);
+        HIPCHECK(launch_elb_store(ctx->stream, d.B, e, cs, sShadow.p, cfg.store_capacity, stored));
     });
     if (keep_first) {  // missingrate_all (mcmcVARshadowrate.m:498)
       sMissing.alloc(B * cap * cfg.Ns * cfg.elbTmax);
       ElbDev e2 = elb_view();
       launch(KID_STORE, [&] {
-        hipLaunchKernelGGL(k_ps_first_store, dim3(d.B), dim3(256), 0, ctx->stream,
-                           ((last_ps || elb_missing || elb_alt) && psFirst.p) ? psFirst.p : nullptr, e2.elbT,
-                           cs.slot, sMissing.p,
-                           cfg.Ns * cfg.elbTmax, cfg.Ns, cfg.store_capacity, stored);
+        HIPCHECK(launch_ps_first_store(ctx->stream, d.B,
+                                       ((last_ps || elb_missing || elb_alt) && psFirst.p) ? psFirst.p : nullptr, e2.elbT,
+                                       cs.slot, sMissing.p, cfg.Ns * cfg.elbTmax, cfg.Ns, cfg.store_capacity, stored));
       });
     }
     if (ps_np > 0) {  // stackAccept (:457): ndxAccept of the stored sweep, 0 = none / Gibbs
       sAccept.alloc(B * cap);
       launch(KID_STORE, [&] {
-        hipLaunchKernelGGL(k_ps_store, dim3((d.B + 255) / 256), dim3(256), 0, ctx->stream,
-                           (last_ps && !elb_missing) ? psFlag.p : nullptr, sAccept.p, d.B, cfg.store_capacity, stored);
+        HIPCHECK(launch_ps_store(ctx->stream, (last_ps && !elb_missing) ? psFlag.p : nullptr, sAccept.p, d.B,
+                                 cfg.store_capacity, stored));
       });
     }
   }
@@ -322,9 +297,7 @@ int ccmm_chains::cta_fallback(const RngArgs& ra) {
     dl(iVdiag.p + (size_t)s * N * KP, (size_t)N * KP, jb.ivd);
     dl(iVb.p + (size_t)s * N * KP, (size_t)N * KP, jb.ivb);
     dl(paiPrev.p + (size_t)c * N * KP, (size_t)N * KP, jb.pai);
-    hipLaunchKernelGGL(k_rng_normals, dim3((K * N + 255) / 256), dim3(256), 0, ctx->stream, ra, c,
-                       (int)CCMM_RNG_PAI, K * N, zHost.p);
-    HIPCHECK(hipGetLastError());
+    HIPCHECK(launch_rng_normals(ctx->stream, ra, c, (int)CCMM_RNG_PAI, K * N, zHost.p));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     dl(zHost.p, (size_t)K * N, jb.z);
     jb.X.assign(N, {});

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "ccmm_diagk.h"
+#include "ccmm_internal.h"
 
 namespace ccmm {
 
@@ -68,16 +69,14 @@ hipError_t diag_launch(hipStream_t st, const double* base, long long ld_draw, lo
                        const int* nvalid, const unsigned char* mask, double* out) {
   const DiagPlan pl = diag_plan(S, C);
   if (pl.grid_x == 0 || pl.grid_y == 0 || M < kDiagNG) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_diag_series, dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), pl.lds, st, base, ld_draw, ld_chain,
-                     S, C, M, nvalid, mask, out);
-  return hipGetLastError();
+  return launch_k(k_diag_series, dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), pl.lds, false, st, base, ld_draw, ld_chain,
+                  S, C, M, nvalid, mask, out);
 }
 
 hipError_t diag_transpose_launch(hipStream_t st, const double* in, int M, int S, double* out) {
   if (M < 1 || S < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_diag_transpose, dim3((M + kTrTile - 1) / kTrTile, (S + kTrTile - 1) / kTrTile),
-                     dim3(kTrTile * 8), 0, st, in, M, S, out);
-  return hipGetLastError();
+  return launch_k(k_diag_transpose, dim3((M + kTrTile - 1) / kTrTile, (S + kTrTile - 1) / kTrTile), dim3(kTrTile * 8), 0,
+                  false, st, in, M, S, out);
 }
 
 }  // namespace ccmm

@@ -249,9 +249,7 @@ int ccmm_draw_trunc_normal_batch(ccmm_ctx* ctx, int n, const double* mu, const d
     HIPCHECK(hipMemcpy(dmu.p, mu, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(dsig.p, sig, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(du.p, u, n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_truncnorm, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, dmu.p,
-                       dsig.p, elb, du.p, dout.p, dfl.p);
-    HIPCHECK(hipGetLastError());
+    HIPCHECK(launch_truncnorm(ctx->stream, n, dmu.p, dsig.p, elb, du.p, dout.p, dfl.p));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost));
     if (flags) HIPCHECK(hipMemcpy(flags, dfl.p, n, hipMemcpyDeviceToHost));

@@ -363,5 +363,8 @@ void eig_host(int M, int N, int p, const EigSrc& src, double* maxroot, int* info
 // device: PAI, maxroot, info (not null) and scratch (eig_plan(n, M).scratch bytes) on the device
 hipError_t eig_launch(hipStream_t st, int M, int N, int p, const EigSrc& src, double* maxroot, int* info,
                       double* scratch);
+// check_stationarity: the chains with acc[c] != 0 take PAI [nPAI], E [nE] and the status word back from the snapshot
+hipError_t eig_launch_stat_select(hipStream_t st, int B, int nPAI, int nE, const int* acc, const double* sPAI,
+                                  const double* sE, const int* sStatus, double* PAI, double* E, int* status);
 
 }  // namespace ccmm

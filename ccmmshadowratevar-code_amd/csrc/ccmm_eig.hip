@@ -20,6 +20,24 @@
 #include "../../include/ccmm.h"
 #include "ccmm_eig.h"
 #include "ccmm_err.h"
+#include "ccmm_internal.h"
+
+namespace {
+
+// accepted chains (acc[c] != 0) take PAI, E and the status word back from the snapshot
+__global__ __launch_bounds__(256) void k_stat_select(int nPAI, int nE, const int* __restrict__ acc,
+                                                     const double* __restrict__ sPAI, const double* __restrict__ sE,
+                                                     const int* __restrict__ sStatus, double* __restrict__ PAI,
+                                                     double* __restrict__ E, int* __restrict__ status) {
+  const int c = blockIdx.y;
+  if (!acc[c]) return;
+  const size_t oP = (size_t)c * nPAI, oE = (size_t)c * nE;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nPAI; i += gridDim.x * blockDim.x) PAI[oP + i] = sPAI[oP + i];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nE; i += gridDim.x * blockDim.x) E[oE + i] = sE[oE + i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) status[c] = sStatus[c];
+}
+
+}  // namespace
 
 namespace ccmm {
 
@@ -68,12 +86,16 @@ hipError_t eig_launch(hipStream_t st, int M, int N, int p, const EigSrc& src, do
   for (int m0 = 0; m0 < M; m0 += pl.chunk) {  // launches on one stream share the scratch in order
     const int m1 = std::min(M, m0 + pl.chunk);
     const int grid = (m1 - m0 + kEigWaves - 1) / kEigWaves;
-    hipLaunchKernelGGL(k_eig_maxroot, dim3(grid), dim3(pl.threads), 0, st, m0, m1, N, p, src, maxroot, info,
-                       scratch);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = launch_k(k_eig_maxroot, dim3(grid), dim3(pl.threads), 0, false, st, m0, m1, N, p, src, maxroot,
+                                  info, scratch);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t eig_launch_stat_select(hipStream_t st, int B, int nPAI, int nE, const int* acc, const double* sPAI,
+                                  const double* sE, const int* sStatus, double* PAI, double* E, int* status) {
+  return launch_k(k_stat_select, dim3(8, B), dim3(256), 0, false, st, nPAI, nE, acc, sPAI, sE, sStatus, PAI, E, status);
 }
 
 void eig_host(int M, int N, int p, const EigSrc& src, double* maxroot, int* info) {

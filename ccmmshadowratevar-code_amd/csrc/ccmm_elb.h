@@ -1,8 +1,9 @@
 // Device views, record layouts, LDS sizes, launch decisions and host launchers of the ELB shadow-rate step and
 // its acceptance-sampling branch.  The kernels are defined in their own translation units, ccmm_elb.hip and
-// ccmm_ps.hip, each with the launchers that pick (and so instantiate) its template arguments; this header is
-// what the host side (ccmm_chains_elb.hip) and the predictive-density kernels see.  The size and decision functions
-// make no HIP call (tests/launch_plans_main.cpp prints them on the host).
+// ccmm_ps.hip, each with the launchers of every kernel it defines (those of the templated kernels pick, and so
+// instantiate, the template arguments); this header is what the host side (ccmm_chains_elb.hip,
+// ccmm_chains_sweep.hip) and the predictive-density kernels see: launchers, no kernel.  The size and decision
+// functions make no HIP call (tests/launch_plans_main.cpp prints them on the host).
 #pragma once
 #include <algorithm>
 
@@ -33,7 +34,7 @@ struct ElbDev {
   double* Scur;   // [B][elbTmax][Ns] shadow rates (in/out)
   int condStride;
   int kshadow, K;  // hybrid model: PAI rows kshadow..K-1 load the actual-rate lags (K > kshadow)
-  int mode;        // CCMM_ELB_MODE timing ablation (0 in production)
+  int mode;        // kElb* bits below; 0 in production
   const double* yhat;  // [B][elbTmax][N] explicit YHAT0 (ccmm_gibbs_shadowrates) or nullptr
   uint8_t* flags;      // [B][passes][elbTmax][Ns] truncated-normal branch flags or nullptr
   // acceptance-sampling branch (mcmcVARshadowrateBlockHybrid.m:438-466, ccmm_ps.hip)
@@ -58,6 +59,12 @@ struct ElbDev {
   unsigned long long psEpoch;
   double* ScurSpec;  // [B][elbTmax][Ns]
 };
+
+// bits of ElbDev::mode: none selects what is computed; all are timing-only (CCMM_ELB_MODE, ablation build; a default
+// build compiles them out; results invalid): no draws (fmin), fixed uniforms, cycle attribution of the ASYNC month
+// body (CCMM_ELB_PROF), no record loads, no predecessor wait, no month sums, ub histogram of the draws
+constexpr int kElbNoDraw = 1, kElbFixedU = 2, kElbProf = 64, kElbNoRecords = 128, kElbNoWait = 256, kElbNoSums = 512,
+              kElbUbHist = 4096;
 
 // condition record per censored month (doubles):
 //   a_t [Ns] | beta1 [Ns][Ns-1] | sqrtOmega1 [Ns] | 1 / sqrtOmega1 [Ns] | Ω [Ns][Ns] | G [2p Ns][Ns]
@@ -262,26 +269,29 @@ struct ElbGibbsPlan {
   int parts;   // mp: 2 or 4
 };
 
-// ---------------------------------------------------------------- launchers and kernels (ccmm_elb.hip)
+// ---------------------------------------------------------------- launchers (ccmm_elb.hip)
 inline bool elb_supported_ns(int Ns) { return Ns >= 1 && Ns <= kElbNsMax; }
 hipError_t launch_elb_prep(hipStream_t st, const ElbPrepPlan& pl, Dims d, ElbDev e, XSel xs, ChainState cs);
 hipError_t launch_elb_cond(hipStream_t st, const ElbCondPlan& pl, Dims d, ElbDev e, ChainState cs);
 // xc: the granule exchange of kElbGibbsMp (unused otherwise)
 hipError_t launch_elb_gibbs(hipStream_t st, const ElbGibbsPlan& pl, Dims d, ElbDev e, ChainState cs, RngArgs ra,
                             ElbXch xc);
-__global__ void k_elb_spec_select(ElbDev e, const int* slot, int B);
-__global__ void k_elb_rebuild(Dims d, ElbDev e, XSel xs, ChainState cs, int xslab0, double* dpool, int ldd, int drows,
-                              double* dcpool, int dcld, long long dcslab);
-__global__ void k_elb_store(ElbDev e, ChainState cs, double* out, int cap, int m);
-// ---------------------------------------------------------------- launchers and kernels (ccmm_ps.hip)
+// the speculative draw kept where the PS branch rejected; one workgroup per chain
+hipError_t launch_elb_spec_select(hipStream_t st, ElbDev e, const int* slot, int B);
+// the chains' X / Y slabs (and lag slabs dpool, lag twins dcpool when given) rebuilt from the new shadow rates
+hipError_t launch_elb_rebuild(hipStream_t st, Dims d, ElbDev e, XSel xs, ChainState cs, int xslab0, double* dpool, int ldd,
+                              int drows, double* dcpool, int dcld, long long dcslab);
+hipError_t launch_elb_store(hipStream_t st, int B, ElbDev e, ChainState cs, double* out, int cap, int m);
+// ---------------------------------------------------------------- launchers (ccmm_ps.hip)
 // the fused draw k_ps_draw1<ps.W> (W <= 64)
 hipError_t launch_ps_draw1(hipStream_t st, Dims d, ElbDev e, PsDev ps, ChainState cs, RngArgs ra);
 // k_ps_chol_w<ps.W> (W <= 64; register window, one wave per chain) or, lds_window, k_ps_chol (same factor)
 hipError_t launch_ps_chol(bool lds_window, hipStream_t st, Dims d, ElbDev e, PsDev ps, ChainState cs);
 // prop: k_ps_prop<ps.W> over the ps.NP proposals; then k_ps_apply<ps.W, FORCED = ps.draw1 != 0>
 hipError_t launch_ps_apply(bool prop, hipStream_t st, int B, ElbDev e, PsDev ps, RngArgs ra, int kept);
-__global__ void k_ps_first_store(const double* first, const int* elbT, const int* slot, double* out, int per,
-                                 int Ns, int cap, int m);
-__global__ void k_ps_store(const int* flag, int* out, int B, int cap, int m);
+// proposal 1 (first, or NaN when null) and ndxAccept (flag, or 0 when null) of sweep m into the draw store
+hipError_t launch_ps_first_store(hipStream_t st, int B, const double* first, const int* elbT, const int* slot,
+                                 double* out, int per, int Ns, int cap, int m);
+hipError_t launch_ps_store(hipStream_t st, const int* flag, int* out, int B, int cap, int m);
 
 }  // namespace ccmm

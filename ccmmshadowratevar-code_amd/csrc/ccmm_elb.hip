@@ -565,16 +565,14 @@ __device__ __forceinline__ double elb_trunc_normal_pz(double mu, double sig, dou
   return elb_gibbs_trunc_normal(mu, sig, isig, elb, u, fl);
 }
 
-// timing-only ablation bits of ElbDev::mode (CCMM_ELB_MODE, read by the ablation build only; a
-// default build compiles them out): 1 no draws (fmin), 2 fixed uniforms, 64 cycle attribution,
-// 128 no record loads, 256 no predecessor wait, 512 no month sums, 4096 ub histogram of the draws
+// the timing-only bits of ElbDev::mode (ccmm_elb.h kElb*): read by the ablation build only
 #ifdef CCMM_ABLATION
-#define ELB_CLK(x) const unsigned long long x = (e.mode & 64) ? clock64() : 0ull
+#define ELB_CLK(x) const unsigned long long x = (e.mode & kElbProf) ? clock64() : 0ull
 #define ELB_ABL(bit) ((e.mode & (bit)) != 0)
-// 64 (CCMM_ELB_PROF=1): per wave of the ASYNC month body, shader-clock cycles spent waiting for the
+// kElbProf (CCMM_ELB_PROF=1): per wave of the ASYNC month body, shader-clock cycles spent waiting for the
 // predecessor, in the neighbour sums, in the draws and in the store/publish tail, plus the month count
 __device__ unsigned long long g_elb_prof[8 * 6];
-__device__ unsigned long long g_elb_ubhist[8];  // 4096: draws by ub = (elb - mu) / sig bin
+__device__ unsigned long long g_elb_ubhist[8];  // kElbUbHist: draws by ub = (elb - mu) / sig bin
 extern "C" int ccmm_elb_ubhist(unsigned long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_elb_ubhist), sizeof(g_elb_ubhist)) != hipSuccess) return -1;
   if (reset) {
@@ -722,8 +720,8 @@ __device__ __forceinline__ void elb_month_sums(const ElbDev& e, const ElbRec<NS>
                                                const double* Sl, const double* Ul, const double* Zl, int t, int T,
                                                ElbMonth<NS>& m) {
   for (int a = 0; a < NS; ++a) {
-    m.u[a] = ELB_ABL(2) ? 0.5 : Ul[t * NS + a];
-    m.zu[a] = ELB_ABL(2) ? 0.0 : Zl[t * NS + a];
+    m.u[a] = ELB_ABL(kElbFixedU) ? 0.5 : Ul[t * NS + a];
+    m.zu[a] = ELB_ABL(kElbFixedU) ? 0.0 : Zl[t * NS + a];
   }
   const int tn0 = t + g.off0, tn1 = t + g.off1;
   const double v0 = (g.h0 && tn0 >= 0 && tn0 < T) ? Sl[tn0 * NS + g.sp0] : 0.0;
@@ -731,7 +729,7 @@ __device__ __forceinline__ void elb_month_sums(const ElbDev& e, const ElbRec<NS>
   if constexpr (CUR_FIRST)
     for (int a = 0; a < NS; ++a) m.cur[a] = Sl[t * NS + a];
   for (int a = 0; a < NS; ++a) m.sp[a] = fma(g.h0 ? rc.g0[a] : 0.0, v0, (g.h1 ? rc.g1[a] : 0.0) * v1);
-  if (!ELB_ABL(512)) wave_sum_dpp_n(m.sp);
+  if (!ELB_ABL(kElbNoSums)) wave_sum_dpp_n(m.sp);
   for (int a = 0; a < NS; ++a) m.sp[a] = rc.hd[a] + m.sp[a];
   if constexpr (!CUR_FIRST)
     for (int a = 0; a < NS; ++a) m.cur[a] = Sl[t * NS + a];
@@ -759,13 +757,13 @@ __device__ __forceinline__ void elb_month_draws(const ElbDev& e, int c, int n, i
     }
     uint8_t fl = 0;
 #ifdef CCMM_ABLATION
-    if (ELB_ABL(4096) && rec) {
+    if (ELB_ABL(kElbUbHist) && rec) {
       const double ub = (e.elb - mu) * fabs(so[NS + a]);
       const int bin = ub >= 9.0 ? 0 : ub >= 7.0 ? 1 : ub >= 5.0 ? 2 : ub >= 3.0 ? 3 : ub >= 1.0 ? 4 : ub >= -1.0 ? 5 : 6;
       atomicAdd(&g_elb_ubhist[bin], 1ull);
     }
 #endif
-    cur[a] = ELB_ABL(1) ? fmin(mu, e.elb) : draw(a, mu, so[a], so[NS + a], fl);
+    cur[a] = ELB_ABL(kElbNoDraw) ? fmin(mu, e.elb) : draw(a, mu, so[a], so[NS + a], fl);
     if (e.flags && rec) e.flags[(((size_t)c * e.passes + n) * e.elbTmax + t) * NS + a] = fl;
   }
 }
@@ -866,7 +864,7 @@ __global__ __launch_bounds__(64) void k_elb_gibbs(Dims d, ElbDev e, ChainState c
 // covers it; its own progress goes to *oprog.  The censored-month entries are fetched two months ahead, so
 // no LDS round trip of them sits on the month's path.  Spec mode stops once the PS branch has accepted a
 // proposal.  Every spin is bounded: a stuck wave sets CCMM_STATUS_HANDOFF and publishes "done", so its
-// successors drain.  pw: the wave's row of the cycle attribution (ablation build, mode 64)
+// successors drain.  pw: the wave's row of the cycle attribution (ablation build, kElbProf)
 template <int NS, int W>
 __device__ __forceinline__ void elb_async_passes(const ElbDev& e, const ChainState& cs, int c, int n0, int pw, int T,
                                                  int nc, int lane, const Rng& rng, const double* recs, double* Sl,
@@ -889,7 +887,7 @@ __device__ __forceinline__ void elb_async_passes(const ElbDev& e, const ChainSta
       const int ni = (i + 1 < nc) ? i + 1 : 0;
       const int nni = (ni + 1 < nc) ? ni + 1 : 0;
       const int tmnn = Tm[nni];
-      if (!ELB_ABL(128))
+      if (!ELB_ABL(kElbNoRecords))
         elb_load_rec<NS>(e, recs, ni, g, rn);  // next month of this wave (month 0 of its next pass after the last)
       else
         rn = rc;  // (128: timing only, no record loads)
@@ -900,7 +898,7 @@ __device__ __forceinline__ void elb_async_passes(const ElbDev& e, const ChainSta
         }
         dec = elb_ps_decision(e, c);
       }
-      if (n > 0 && !ELB_ABL(256)) {  // (256: timing only, no predecessor wait)
+      if (n > 0 && !ELB_ABL(kElbNoWait)) {  // (timing only, no predecessor wait)
         const int need = (n - 1) * nc + reach[i] + 1;
         int it = 0;
         while (__hip_atomic_load(pprog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) {
@@ -925,7 +923,7 @@ __device__ __forceinline__ void elb_async_passes(const ElbDev& e, const ChainSta
       tmn = tmnn;
       if (lane == 0) __hip_atomic_store(oprog, n * nc + i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 #ifdef CCMM_ABLATION
-      if (e.mode & 64) {
+      if (e.mode & kElbProf) {
         ELB_CLK(t4);
         acc_w += t1 - t0;
         acc_s += t2 - t1;
@@ -937,7 +935,7 @@ __device__ __forceinline__ void elb_async_passes(const ElbDev& e, const ChainSta
     }
   }
 #ifdef CCMM_ABLATION
-  if ((e.mode & 64) && lane == 0 && c == 0 && pw < 8) {
+  if ((e.mode & kElbProf) && lane == 0 && c == 0 && pw < 8) {
     const unsigned long long acc[6] = {acc_w, acc_s, acc_d, acc_t, months, 1ull};
     for (int q = 0; q < 6; ++q) atomicAdd(&g_elb_prof[pw * 6 + q], acc[q]);
   }
@@ -1240,7 +1238,7 @@ __global__ __launch_bounds__(64) void k_elb_gibbs_oct(Dims d, ElbDev e, ChainSta
     const int tt = Tm[ii] & 0xffff;
 #pragma unroll
     for (int a = 0; a < NS; ++a)
-      uu[a] = ELB_ABL(2) ? 0.5 : rng.uniform(CCMM_RNG_ELB, (uint32_t)(tt * NS + a + T * NS * nn));
+      uu[a] = ELB_ABL(kElbFixedU) ? 0.5 : rng.uniform(CCMM_RNG_ELB, (uint32_t)(tt * NS + a + T * NS * nn));
   };
   double ucur[NS];
   if (n < P) draw_u(n, 0, ucur);
@@ -1426,6 +1424,22 @@ struct GibbsLaunch {
 hipError_t launch_elb_gibbs(hipStream_t st, const ElbGibbsPlan& pl, Dims d, ElbDev e, ChainState cs, RngArgs ra,
                             ElbXch xc) {
   return for_ns<GibbsLaunch>(e.Ns, st, pl, d, e, cs, ra, xc);
+}
+
+hipError_t launch_elb_spec_select(hipStream_t st, ElbDev e, const int* slot, int B) {
+  return launch_k(k_elb_spec_select, dim3(B), dim3(256), 0, false, st, e, slot, B);
+}
+
+// one thread per (lag 0..p, shadow rate, window month) of the longest window
+hipError_t launch_elb_rebuild(hipStream_t st, Dims d, ElbDev e, XSel xs, ChainState cs, int xslab0, double* dpool, int ldd,
+                              int drows, double* dcpool, int dcld, long long dcslab) {
+  const int nrb = e.elbTmax * e.Ns * (e.p + 1);
+  return launch_k(k_elb_rebuild, dim3((nrb + 255) / 256, d.B), dim3(256), 0, false, st, d, e, xs, cs, xslab0, dpool, ldd,
+                  drows, dcpool, dcld, dcslab);
+}
+
+hipError_t launch_elb_store(hipStream_t st, int B, ElbDev e, ChainState cs, double* out, int cap, int m) {
+  return launch_k(k_elb_store, dim3(B), dim3(256), 0, false, st, e, cs, out, cap, m);
 }
 
 }  // namespace ccmm

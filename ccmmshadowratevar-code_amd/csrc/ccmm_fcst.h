@@ -1,5 +1,5 @@
-// Arguments, LDS budgets, the host launcher and kernel declarations of the predictive-density kernels (their
-// own translation unit, ccmm_fcst.hip).  The size and decision functions make no HIP call.
+// Arguments, LDS budgets and the host launchers of the predictive-density kernels (their own translation unit,
+// ccmm_fcst.hip, which launches every one of them).  The size and decision functions make no HIP call.
 #pragma once
 #include <algorithm>
 
@@ -54,10 +54,14 @@ struct FcstArgs {
   double* scores;         // [B][Nd][4]
   int* status;            // [B]  bit 1: NaN score (more than kMvnMaxD censored series)
   GLNodes gl;
-  int mode;               // timing-only ablation (CCMM_FCST_MODE; results invalid): 1 no scores, 2 no horizons
+  int mode;               // kFcst* bits below; 0 in production
   int hc;                 // horizons per shock chunk of k_fcst (fcst_paths_lds_doubles)
   double* sv1;            // [B][Nd][N] SV at horizon 1 of each draw (k_fcst -> k_fcst_scores)
 };
+
+// bits of FcstArgs::mode: none selects what is computed; both are timing-only (CCMM_FCST_MODE, ablation build;
+// results invalid): k_fcst_scores returns at once, k_fcst simulates no horizon
+constexpr int kFcstNoScores = 1, kFcstNoHorizons = 2;
 
 // k_fcst<kFcstRegN> (N <= 21, p <= 3 kFcstRegLags, not hybrid) holds each lane's PAI column
 // entries for its lags in registers instead of staging PAI in LDS: the lag sums then read only
@@ -95,15 +99,14 @@ inline int fcst_variant(int N, int p, int bh, bool reg_opt) {
 // k_fcst<RN> then k_fcst_scores of one kept draw per chain; sets a.hc and a.sv1.  reg_opt: option fcst_reg.
 // Throws std::runtime_error when the paths' state does not fit one CU's LDS
 hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt);
-__global__ void k_fcst_jumpoff(int N, int p, int K, int TP, const int* __restrict__ Tslot,
-                               const int* __restrict__ slot, const double* __restrict__ ypool,
-                               const int* __restrict__ yidx, int ldXj, double* __restrict__ Xj, int Ns,
-                               const int* __restrict__ ndxS, double elb);
-__global__ void k_fcst_accum(int N, int H, int Nd, int cap, int m, const double* __restrict__ fY,
-                             const double* __restrict__ fYc, const double* __restrict__ yhat,
-                             const double* __restrict__ sc, double* __restrict__ sum,
-                             double* __restrict__ sumc, double* __restrict__ sumhat,
-                             double* __restrict__ scStore, double* __restrict__ paths,
-                             double* __restrict__ pathsc);
+// Xjumpoff of every chain from its Y slab (and, block hybrid / hybrid with Ns > 0, the slot's actual data); one
+// workgroup per chain
+// (a: sizes, slot, Ns, ndxS, elb and ldXj; Xj is written)
+hipError_t launch_fcst_jumpoff(hipStream_t st, const FcstArgs& a, int TP, const int* Tslot, const double* ypool,
+                               const int* yidx, double* Xj);
+// the kept draw's paths a.fY, a.fYc (and yhat when given) into the running sums, its scores (and paths) into the
+// store at index m
+hipError_t launch_fcst_accum(hipStream_t st, const FcstArgs& a, int cap, int m, const double* yhat, double* sum,
+                             double* sumc, double* sumhat, double* scStore, double* paths, double* pathsc);
 
 }  // namespace ccmm

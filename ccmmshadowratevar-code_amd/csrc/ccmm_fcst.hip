@@ -439,7 +439,7 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
   }
   int head = 0;
   __syncthreads();
-  for (int h0 = 0; h0 < ((a.mode & 2) ? 0 : H); h0 += hc) {
+  for (int h0 = 0; h0 < ((a.mode & kFcstNoHorizons) ? 0 : H); h0 += hc) {
     const int nh = min(hc, H - h0);
     if (!mean_path) {
       // SV normals randn(N, H*Nd) column hh + job H (mcmcVAR.m:302) and the shock normals
@@ -585,7 +585,7 @@ __global__ __launch_bounds__(64) void k_fcst_scores(FcstArgs a) {
   const int job = blockIdx.x, c = blockIdx.y;
   const int N = a.N, K = a.K, Kx = a.Kx, Nd = a.Nd;
   const int lane = threadIdx.x;
-  if (job >= Nd || (a.mode & 1)) return;
+  if (job >= Nd || (a.mode & kFcstNoScores)) return;
   double* invA = sm;                  // N x N
   double* mu = invA + N * N;          // muY (N)
   double* y = mu + N;                 // yrealized(:,1) (N)
@@ -758,7 +758,7 @@ __global__ void k_fcst_accum(int N, int H, int Nd, int cap, int m, const double*
 }
 
 
-// ------------------------------------------------------------------ host launcher
+// ------------------------------------------------------------------ host launchers
 // the paths (one single-wave workgroup per (draw, chain); job Nd = the linear model's mean path) then the scores
 hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt) {
   const bool reg = fcst_reg_path(a.N, a.p, a.bh) && reg_opt;
@@ -774,6 +774,18 @@ hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt) {
                                            : launch_k(k_fcst<0>, g, dim3(64), lp, true, st, a);
   if (e != hipSuccess) return e;
   return launch_k(k_fcst_scores, dim3(a.Nd, a.B), dim3(64), ls, true, st, a);
+}
+
+hipError_t launch_fcst_jumpoff(hipStream_t st, const FcstArgs& a, int TP, const int* Tslot, const double* ypool,
+                               const int* yidx, double* Xj) {
+  return launch_k(k_fcst_jumpoff, dim3(a.B), dim3(256), 0, false, st, a.N, a.p, a.K, TP, Tslot, a.slot, ypool, yidx, a.ldXj,
+                  Xj, a.Ns, a.ndxS, a.elb);
+}
+
+hipError_t launch_fcst_accum(hipStream_t st, const FcstArgs& a, int cap, int m, const double* yhat, double* sum,
+                             double* sumc, double* sumhat, double* scStore, double* paths, double* pathsc) {
+  return launch_k(k_fcst_accum, dim3(a.B), dim3(256), 0, false, st, a.N, a.H, a.Nd, cap, m, a.fY, a.fYc, yhat, a.scores, sum, sumc,
+                  sumhat, scStore, paths, pathsc);
 }
 
 }  // namespace ccmm

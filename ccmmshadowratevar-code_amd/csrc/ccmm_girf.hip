@@ -408,12 +408,7 @@ hipError_t girf_launch(hipStream_t st, const GirfArgs& a) {
   g.seed = a.seed; g.part = a.part;
   const GirfPlan pl = girf_plan(a.N, a.p, g.Ny, a.force_generic != 0);
   const dim3 grid(g.nchunk, 3, a.M), block(pl.threads);
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-    if (e2 != hipSuccess) return e2;
-    hipLaunchKernelGGL(kern, grid, block, pl.lds, st, g);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return launch_k(kern, grid, block, pl.lds, true, st, g); };
   hipError_t e;
   if (pl.fast_ny4 == 8) e = go(k_girf_fast<kGirfFastP, kGirfFastN4, 8>);
   else if (pl.fast_ny4 == 4) e = go(k_girf_fast<kGirfFastP, kGirfFastN4, 4>);
@@ -424,9 +419,8 @@ hipError_t girf_launch(hipStream_t st, const GirfArgs& a) {
   else return hipErrorInvalidValue;
   if (e != hipSuccess) return e;
   const int nt = a.N * 3 * a.M;
-  hipLaunchKernelGGL(k_girf_reduce, dim3((nt + 255) / 256), dim3(256), 0, st, a.M, a.N, a.H, g.nchunk, a.nsim,
-                     a.part, a.cumcode, a.np_, a.out);
-  return hipGetLastError();
+  return launch_k(k_girf_reduce, dim3((nt + 255) / 256), dim3(256), 0, false, st, a.M, a.N, a.H, g.nchunk, a.nsim, a.part,
+                  a.cumcode, a.np_, a.out);
 }
 
 }  // namespace ccmm

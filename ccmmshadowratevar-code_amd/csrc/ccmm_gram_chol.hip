@@ -45,7 +45,7 @@ __device__ __forceinline__ int gram_chol_body(const GcArgs& g, double* sm, int t
   double* Z0 = sm;
   double* Z1 = sm + kGcTC * LDZ;
   constexpr int NLOAD = (kGcTC * 16 * NT + 511) / 512;
-  const int nch = (g.mode & 1) ? 0 : (g.T + kGcTC - 1) / kGcTC;
+  const int nch = (g.mode & kGcNoSyrk) ? 0 : (g.T + kGcTC - 1) / kGcTC;
   double vals[NLOAD];
   auto load_chunk = [&](int ch) {
     const int t0 = ch * kGcTC;
@@ -109,7 +109,7 @@ __device__ __forceinline__ int gram_chol_body(const GcArgs& g, double* sm, int t
   double* Dg = sm;                // 16 x kGcLdp   L_pp
   double* Pn = sm + 16 * kGcLdp;  // NT slots of 16 x kGcLdp   L_ip
   int bad = 0;
-  const int npanel = (g.mode & 2) ? 0 : NT;
+  const int npanel = (g.mode & kGcNoChol) ? 0 : NT;
   for (int p = 0; p < npanel; ++p) {
     // (1) diagonal tile -> LDS
 #pragma unroll
@@ -121,7 +121,7 @@ __device__ __forceinline__ int gram_chol_body(const GcArgs& g, double* sm, int t
       }
     }
     __syncthreads();
-    if (W == 0 && !(g.mode & 16)) {
+    if (W == 0 && !(g.mode & kGcNoDiag)) {
       double row[16];
       double mydiag = 1.0;
 #pragma unroll
@@ -173,7 +173,7 @@ __device__ __forceinline__ int gram_chol_body(const GcArgs& g, double* sm, int t
     }
     __syncthreads();
     {
-      const int nrows = (g.mode & 8) ? 0 : (NT - 1 - p) * 16;
+      const int nrows = (g.mode & kGcNoPanel) ? 0 : (NT - 1 - p) * 16;
       for (int e = tid; e < nrows; e += 512) {
         const int ti = p + 1 + (e >> 4), rr = e & 15;
         double* P = Pn + ti * 16 * kGcLdp + rr * kGcLdp;
@@ -198,7 +198,7 @@ __device__ __forceinline__ int gram_chol_body(const GcArgs& g, double* sm, int t
     }
     __syncthreads();
     // (3) trailing update, groups of 4 tiles
-    if (p + 1 < NT && !(g.mode & 4)) {
+    if (p + 1 < NT && !(g.mode & kGcNoTrailing)) {
 #pragma unroll
       for (int g0 = 0; g0 < TPW; g0 += 4) {
         // live iff tj > p; tj is non-decreasing in k, so test the last slot of the group
@@ -272,20 +272,16 @@ __global__ __launch_bounds__(512, 1) void k_gram_chol(Dims d, const int* __restr
 // ------------------------------------------------------------------ host launcher
 bool gram_chol_supported(int NT) { return NT == 4 || NT == 8 || NT == 12 || NT == 16; }
 
-template <int NT>
-static hipError_t gram_chol_nt(hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs, const double* iVdiag,
-                               double* rdiag, int mode) {
-  return launch_k(k_gram_chol<NT>, dim3(d.nmat), dim3(512), gram_chol_lds_bytes(NT), true, st, d, Tslot, xs, cs, iVdiag,
-                  rdiag, mode);
-}
-
 hipError_t launch_gram_chol(int NT, hipStream_t st, Dims d, const int* Tslot, XSel xs, ChainState cs,
                             const double* iVdiag, double* rdiag, int mode) {
+  auto go = [&](auto k) {
+    return launch_k(k, dim3(d.nmat), dim3(512), gram_chol_lds_bytes(NT), true, st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
+  };
   switch (NT) {
-    case 4: return gram_chol_nt<4>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
-    case 8: return gram_chol_nt<8>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
-    case 12: return gram_chol_nt<12>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
-    case 16: return gram_chol_nt<16>(st, d, Tslot, xs, cs, iVdiag, rdiag, mode);
+    case 4: return go(k_gram_chol<4>);
+    case 8: return go(k_gram_chol<8>);
+    case 12: return go(k_gram_chol<12>);
+    case 16: return go(k_gram_chol<16>);
     default: return hipErrorInvalidValue;
   }
 }

@@ -22,11 +22,17 @@ constexpr size_t kLdsCu = 160 * 1024;      // LDS of one CU (gfx950): the most o
 constexpr size_t kLdsDefault = 64 * 1024;  // dynamic LDS of a launch without hipFuncAttributeMaxDynamicSharedMemorySize
 
 #ifdef __HIPCC__
-// one launch of kernel k with `lds` bytes of dynamic LDS; raise: lift the kernel's dynamic-LDS limit first
+// lift kernel k's dynamic-LDS limit to `lds` bytes: before a launch above kLdsDefault or an occupancy query for one
+template <class K>
+inline hipError_t raise_lds(K k, size_t lds) {
+  return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+// one launch of kernel k with `lds` bytes of dynamic LDS; raise: lift the kernel's dynamic-LDS limit first.  Every
+// launch of the library goes through here, from the unit that defines k
 template <class K, class... A>
 inline hipError_t launch_k(K k, dim3 grid, dim3 block, size_t lds, bool raise, hipStream_t st, A... a) {
   if (raise) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = raise_lds(k, lds);
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k, grid, block, lds, st, a...);

@@ -650,11 +650,11 @@ __global__ __launch_bounds__(256) void k_phi(Dims d, const int* __restrict__ Tsl
     for (; t < T; ++t) a0 = fma(er[t], ec[t], a0);
     Lpost[r * NS + col] = sP[r + col * N] + ((a0 + a1) + (a2 + a3));
   }
-  // stage_eta bit 1: Z (N x TZ, k_phi_gen) follows eta into the same LDS region, one coalesced pass,
+  // kPhiStageZ: Z (N x TZ, k_phi_gen) follows eta into the same LDS region, one coalesced pass,
   // so that the ZZ' chains read LDS instead of strided HBM rows (~0.2 ms of global-load latency per
   // launch at B = 1); the same products in the same order
   const double* Zw = Z;
-  if (stage_eta & 2) {
+  if (stage_eta & kPhiStageZ) {
     double* zs = Ph + N * NS;
     __syncthreads();
     for (int q0 = tid; q0 < N * TZ; q0 += 16 * (int)blockDim.x) {
@@ -873,6 +873,44 @@ hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const 
   const PhiPlan pl = phi_plan(d.N, d.TP, dPHI);
   return launch_k(k_phi, dim3(d.B), dim3(256), pl.lds, pl.lds > kLdsDefault, st, d, Tslot, dPHI, sPHIall, cs,
                   pl.stage_eta);
+}
+
+
+hipError_t launch_sv_mix(hipStream_t st, Dims d, const int* Tslot, ChainState cs, RngArgs ra) {
+  return launch_k(k_sv_mix, dim3((d.N * d.TP + 255) / 256, d.B), dim3(256), 0, false, st, d, Tslot, cs, ra);
+}
+
+hipError_t launch_phi_gen(hipStream_t st, Dims d, const int* Tslot, int dPHI, ChainState cs, RngArgs ra) {
+  return launch_k(k_phi_gen, dim3((d.N * (d.TP + dPHI) + 255) / 256, d.B), dim3(256), 0, false, st, d, Tslot, dPHI, cs,
+                  ra);
+}
+
+hipError_t launch_store(hipStream_t st, Dims d, ChainState cs, Store s) {
+  return launch_k(k_store, dim3(64, d.B), dim3(256), 0, false, st, d, cs, s);
+}
+
+hipError_t launch_pai_moments(hipStream_t st, const double* sPAI, int cap, int m0, int m1, int per, int B, double* sum,
+                              double* sumsq) {
+  return launch_k(k_pai_moments, dim3((unsigned)(((size_t)B * per + 255) / 256)), dim3(256), 0, false, st, sPAI, cap, m0,
+                  m1, per, B, sum, sumsq);
+}
+
+hipError_t launch_truncnorm(hipStream_t st, int n, const double* mu, const double* sig, double elb, const double* u,
+                            double* out, uint8_t* flags) {
+  return launch_k(k_truncnorm, dim3((n + 255) / 256), dim3(256), 0, false, st, n, mu, sig, elb, u, out, flags);
+}
+
+hipError_t launch_rng_normals(hipStream_t st, RngArgs ra, int c, int block, int n, double* out) {
+  return launch_k(k_rng_normals, dim3((n + 255) / 256), dim3(256), 0, false, st, ra, c, block, n, out);
+}
+
+hipError_t launch_mfma_selftest(hipStream_t st, const double* A, const double* B, double* D) {
+  return launch_k(k_mfma_selftest, dim3(1), dim3(64), 0, false, st, A, B, D);
+}
+
+hipError_t launch_mfma_selftest_acc(hipStream_t st, const double* A, const double* B, const double* C, double* D,
+                                    int nprobe) {
+  return launch_k(k_mfma_selftest_acc, dim3(nprobe), dim3(64), 0, false, st, A, B, C, D, nprobe);
 }
 
 }  // namespace ccmm

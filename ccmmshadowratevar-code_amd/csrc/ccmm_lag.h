@@ -1,5 +1,5 @@
 // Lag-structured CTA path (kernels in ccmm_lag.hip, its own translation unit):
-// device views, LDS budgets and host launchers used by ccmm_chains.hip and ccmm_chains_sweep.hip.
+// device views, mode bits, LDS budgets and host launchers used by ccmm_chains.hip and ccmm_chains_sweep.hip.
 #pragma once
 #include <algorithm>
 
@@ -12,11 +12,17 @@ struct LagSel {
   const int* idx;       // [B*N] D slab of CTA system (c, j)
   const int* colmap;    // [16*NT] offset of lag column a relative to row t (doubles)
   int ldd, rows, p;     // row stride (odd), rows per slab (TP + p), lag order
-  int mode;             // timing-only ablation (CCMM_LAG_MODE, results invalid): gram 1 no SYRK,
-                        // 2 no Cholesky; solve 16 no v, 32 no X'v, 64 no triangular
-                        // substitutions, 128 no X x.  gram 8: write the raw SYRK stage (Gram tiles,
-                        // b, c) and stop (ccmm_chains_get_cta_gram, parity tests)
+  int mode;             // kLag* bits below; 0 in production
 };
+// bits of LagSel::mode that select what is computed:
+constexpr int kLagGramExport = 8;  // k_gram_chol_lag writes the raw SYRK stage (Gram tiles, b, c) and stops
+                                   // (ccmm_chains_get_cta_gram, parity tests)
+// timing-only bits (CCMM_LAG_MODE, ablation build; results invalid).  k_gram_chol_lag:
+constexpr int kLagNoSyrk = 1, kLagNoChol = 2;  // no SYRK K-steps, no Cholesky
+constexpr int kLagNoFactorInv = 256;   // no serial 16 x 16 factorisation and inverse of the diagonal tiles
+constexpr int kLagNoTrailing = 1024;   // no look-ahead and no trailing updates G_ij -= U_pi' U_pj after a panel
+// k_cta_solve_lag: no v_t, no X'v, no triangular substitutions, no residuals X x
+constexpr int kLagNoV = 16, kLagNoXtv = 32, kLagNoSubst = 64, kLagNoXx = 128;
 
 // k_cta_solve_lag split over two workgroups per chain (small B): X'v half partials, [B][2 halves]
 // [2 equation parities][256], and one progress flag per workgroup; part == nullptr: one workgroup

@@ -132,7 +132,7 @@ __device__ __forceinline__ void gl_syrk(const GlArgs& g, dbl4 (&acc)[gl_tpw(NT)]
   bs0 = 0.0;
   bs1 = 0.0;
   csum = 0.0;
-  const int nks = (g.mode & 1) ? 0 : (g.T + 3) >> 2;
+  const int nks = (g.mode & kLagNoSyrk) ? 0 : (g.T + 3) >> 2;
   // software pipeline over k-steps: step ks scales its raw D values into the MFMA operands,
   // then issues the LDS loads of step ks + 1 into the freed registers before its 15 MFMAs,
   // so those loads complete under ~15 x 64 MFMA cycles instead of stalling the next step
@@ -193,7 +193,7 @@ __device__ __forceinline__ int gram_lag_factor(const GlArgs& g, double* sm, int 
     sti[k] = gi < NTILE ? gl_ti(NT, gi) : 0;
     stj[k] = gi < NTILE ? gl_tj(NT, gi) : 0;
   }
-  if (g.mode & 8) {  // parity export (ccmm_chains_get_cta_gram): the SYRK stage as it stands
+  if (g.mode & kLagGramExport) {  // parity export (ccmm_chains_get_cta_gram): the SYRK stage as it stands
     double* o = g.out;
 #pragma unroll
     for (int k = 0; k < TPW; ++k) {
@@ -256,7 +256,7 @@ __device__ __forceinline__ int gram_lag_factor(const GlArgs& g, double* sm, int 
   // (gl_factor_inv -> LinvB) while the other waves run their trailing updates, so each
   // panel costs two barriers and one serial 16 x 16 factorisation on one wave.
   double* LinvB = Dg;
-  const bool do_chol = !(g.mode & 2);
+  const bool do_chol = !(g.mode & kLagNoChol);
   if (do_chol) {  // prologue: factor the first diagonal tile
     bool own = false;
 #pragma unroll
@@ -269,7 +269,7 @@ __device__ __forceinline__ int gram_lag_factor(const GlArgs& g, double* sm, int 
       }
     }
     wave_lds_sync();
-    if (own && !(g.mode & 256)) bad |= gl_factor_inv(Ws, LinvB, lane);
+    if (own && !(g.mode & kLagNoFactorInv)) bad |= gl_factor_inv(Ws, LinvB, lane);
   }
   for (int p = 0; p < (do_chol ? NT : 0); ++p) {
     const int lr = gl_opaque(lr0), lq = gl_opaque(lq0);  // no hoisted per-slot addresses
@@ -301,7 +301,7 @@ __device__ __forceinline__ int gram_lag_factor(const GlArgs& g, double* sm, int 
       }
     }
     __syncthreads();  // panel visible; LinvB free for the next factorisation
-    if (p + 1 < NT && !(g.mode & 1024)) {
+    if (p + 1 < NT && !(g.mode & kLagNoTrailing)) {
       const int q = p + 1;
       // look-ahead: next diagonal tile first, then its factorisation
       bool own = false;
@@ -320,7 +320,7 @@ __device__ __forceinline__ int gram_lag_factor(const GlArgs& g, double* sm, int 
         }
       }
       wave_lds_sync();
-      if (own && !(g.mode & 256)) bad |= gl_factor_inv(Ws, LinvB, lane);
+      if (own && !(g.mode & kLagNoFactorInv)) bad |= gl_factor_inv(Ws, LinvB, lane);
 #pragma unroll
       for (int k = 0; k < TPW; ++k) {
         const int gi = W + kGlWaves * k;
@@ -453,17 +453,18 @@ extern "C" int ccmm_solve_prof(unsigned long long* out, int reset) {
 // (one agent-scope flag per workgroup and equation, double-buffered by equation parity), and both
 // run the substitutions on the same right-hand side part_0 + part_1 + iVb, so x is the same in both.
 // Every sum is formed in the order of the one-workgroup kernel: the draws are bit-identical.
-template <int NT, int NMAX, int SW, bool RO>
-__global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __restrict__ Tslot,
-                                                              const double* __restrict__ iVb, XSel xs, LagSel ls,
-                                                              ChainState cs, RngArgs ra, SolveXch xc) {
+constexpr int kSlWaves = kSlThreads / 64;  // 8 waves per workgroup
+template <int NT, int NMAX, bool RO>
+__global__ __launch_bounds__(kSlThreads) void k_cta_solve_lag(Dims d, const int* __restrict__ Tslot,
+                                                                const double* __restrict__ iVb, XSel xs, LagSel ls,
+                                                                ChainState cs, RngArgs ra, SolveXch xc) {
   constexpr int NTILE = gl_ntile(NT);
-  constexpr int NTH = 64 * SW;                      // SW waves (8 or 16)
-  // factor tiles held per wave: slots wave + SW k (barrier-stepped substitutions), or with RO (row
+  // factor tiles held per wave: slots wave + kSlWaves k (barrier-stepped substitutions), or with RO (row
   // ownership) whole block rows, NT tiles per wave: wave 0 row NT - 1, wave w >= 1 rows w - 1 and
   // NT - 1 - w (NT = 15: sizes w + (15 - w))
-  static_assert(!RO || (SW == 8 && (NT == 1 || NT == 15)), "row-owned substitutions: 8 waves, NT 1 or 15");
-  constexpr int TPW = RO ? NT : (gl_ntile(NT) + SW - 1) / SW;
+  static_assert(kSlWaves == 8, "row-owned substitutions and the X'v t-halves: 8 waves");
+  static_assert(!RO || NT == 1 || NT == 15, "row-owned substitutions: NT 1 or 15");
+  constexpr int TPW = RO ? NT : (gl_ntile(NT) + kSlWaves - 1) / kSlWaves;
   constexpr int KL = 16 * NT;
   extern __shared__ double sm[];
   const int N = d.N, TP = d.TP, K = d.K, KP = d.KP;
@@ -491,8 +492,8 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
   const double* ih2 = cs.ih2 + (size_t)c * N * TP;
   const double* Y = xs.ypool + (size_t)xs.yidx[c] * N * TP;
   double* E = cs.E + (size_t)c * N * TP;
-  for (int q = tid; q < N * N; q += NTH) Al[(q % N) + (q / N) * NMAX] = cs.A[(size_t)c * N * N + q];
-  for (int q = tid; q < KL; q += NTH) cm[q] = ls.colmap[q];
+  for (int q = tid; q < N * N; q += kSlThreads) Al[(q % N) + (q / N) * NMAX] = cs.A[(size_t)c * N * N + q];
+  for (int q = tid; q < KL; q += kSlThreads) cm[q] = ls.colmap[q];
   // this wave's slots: (ti, tj) per register tile
   int sti[TPW], stj[TPW];
   // RO rows: rHi (register tiles 0 .. nHi - 1) and rLo (tiles nHi .. nHi + nLo - 1)
@@ -505,7 +506,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
       sti[k] = (k < nHi) ? rHi : rLo;
       stj[k] = (k < nHi) ? k : k - nHi;
     } else {
-      const int gi = wave + SW * k;
+      const int gi = wave + kSlWaves * k;
       sti[k] = gi < NTILE ? gl_ti(NT, gi) : 0;
       stj[k] = gi < NTILE ? gl_tj(NT, gi) : 0;
     }
@@ -513,7 +514,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
   // slot of register tile k, or -1
   auto slot_of = [&](int k) -> int {
     if constexpr (RO) return (k < nHi + nLo) ? gl_tile(NT, sti[k], stj[k]) : -1;
-    const int gi = wave + SW * k;
+    const int gi = wave + kSlWaves * k;
     return gi < NTILE ? gi : -1;
   };
   int cur = -1;
@@ -530,21 +531,21 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
       __syncthreads();
       const double* src = ls.dpool + (size_t)slab * rows * ldd;
       // every load of a thread's share issued before the first LDS store (one round trip per 16)
-      for (int q = tid; q < rows * ldd; q += 16 * NTH) {
+      for (int q = tid; q < rows * ldd; q += 16 * kSlThreads) {
         double v[16];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = (q + NTH * u < rows * ldd) ? src[q + NTH * u] : 0.0;
+        for (int u = 0; u < 16; ++u) v[u] = (q + kSlThreads * u < rows * ldd) ? src[q + kSlThreads * u] : 0.0;
 #pragma unroll
         for (int u = 0; u < 16; ++u)
-          if (q + NTH * u < rows * ldd) Dl[q + NTH * u] = v[u];
+          if (q + kSlThreads * u < rows * ldd) Dl[q + kSlThreads * u] = v[u];
       }
       cur = slab;
     }
     SL_CLK(q0);
     // ---- (1) v_t (E(:,j) = Y(:,j) stands for PAI(:,j) = 0, CTA.m:63)
-    for (int t = tlo + tid; t < thi; t += NTH) {
+    for (int t = tlo + tid; t < thi; t += kSlThreads) {
       double acc = 0.0;
-      if (t < T && !(ls.mode & 16)) {
+      if (t < T && !(ls.mode & kLagNoV)) {
         double e[NMAX];
         // per-lane element offsets (k TP + t) advanced in a register, so that no per-k base address
         // is hoisted into scalar registers (the kernel's scalar file would spill)
@@ -599,7 +600,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
       const int h = split ? hh : tid >> 8, a = tid & 255;
       const int t0 = h ? th : 0, t1 = h ? T : th;
       double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-      if ((ls.mode & 32) || tid >= nxv) {  // threads 512.. (SW = 16) idle: the t-halves fix the order
+      if ((ls.mode & kLagNoXtv) || tid >= nxv) {  // split: the other half's threads idle; the t-halves fix the order
       } else if (a < KL) {
         // four strided chains (t mod 4); the loads of eight months are issued before their
         // fused multiply-adds so that one LDS round trip serves eight products
@@ -705,7 +706,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
       v = fma(t[3], u[12], v);
       return xsum32(xsum16(v));
     };
-    const bool subst = !(ls.mode & 64);
+    const bool subst = !(ls.mode & kLagNoSubst);
     // RO hand-offs between waves: LDS flags with workgroup-scope release / acquire, polled with a
     // bounded spin (a cap that is never expected to be reached ends the wait and flags the chain)
     bool stuck = false;
@@ -753,7 +754,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
     for (int p = 0; p < ((subst && !RO) ? NT - 1 : 0); ++p) {
 #pragma unroll
       for (int k = 0; k < TPW; ++k) {
-        const int gi = wave + SW * k;
+        const int gi = wave + kSlWaves * k;
         if (gi < NTILE && stj[k] == p && sti[k] > p) {
           const double v = colsum(lt[k], rl + 1 + 16 * p + lq);
           if (lq == 0) rl[1 + 16 * sti[k] + lr] -= v;
@@ -764,7 +765,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
     if (subst && !RO) {
 #pragma unroll
       for (int k = 0; k < TPW; ++k) {
-        const int gi = wave + SW * k;
+        const int gi = wave + kSlWaves * k;
         if (gi < NTILE && sti[k] == stj[k]) {
           const double v = colsum(lt[k], rl + 1 + 16 * sti[k] + lq);
           if (lq == 0) xl[1 + 16 * sti[k] + lr] = v;
@@ -807,7 +808,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {
           const bool diag = RO ? (slot_of(k) >= 0 && sti[k] == stj[k])
-                               : (wave + SW * k < NTILE && sti[k] == stj[k]);
+                               : (wave + kSlWaves * k < NTILE && sti[k] == stj[k]);
           if (diag) {
             const double q = fold(lt[k], rl[1 + 16 * sti[k] + lr]);
             if ((lr & 3) == 0) xl[1 + 16 * sti[k] + lq + 4 * (lr >> 2)] = q;
@@ -847,7 +848,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
       for (int p = ((subst && !RO) ? NT - 1 : 0); p >= 1; --p) {
 #pragma unroll
         for (int k = 0; k < TPW; ++k) {
-          const int gi = wave + SW * k;
+          const int gi = wave + kSlWaves * k;
           if (gi < NTILE && sti[k] == p && stj[k] < p) {
             const double q = fold(lt[k], xl[1 + 16 * p + lr]);
             if ((lr & 3) == 0) xl[1 + 16 * stj[k] + lq + 4 * (lr >> 2)] -= q;
@@ -864,7 +865,7 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
     __syncthreads();
     if (tid == KL) {
       double sacc = 0.0;
-      for (int w = 0; w < NTH / 64; ++w) sacc += red[w];
+      for (int w = 0; w < kSlThreads / 64; ++w) sacc += red[w];
       xl[0] = (rl[0] - sacc) * Lv[0];
     }
     __syncthreads();
@@ -872,10 +873,10 @@ __global__ __launch_bounds__(64 * SW) void k_cta_solve_lag(Dims d, const int* __
     // ---- (5) PAI(:,j) = x; E(:,j) = Y(:,j) - X x
     double* pai = cs.PAI + ((size_t)c * N + j) * KP;
     if (hh == 0)
-      for (int k = tid; k < KP; k += NTH) pai[k] = (k < K) ? xl[k] : 0.0;
-    for (int t = tlo + tid; t < thi; t += NTH) {
+      for (int k = tid; k < KP; k += kSlThreads) pai[k] = (k < K) ? xl[k] : 0.0;
+    for (int t = tlo + tid; t < thi; t += kSlThreads) {
       double o = 0.0;
-      if (t < T && !(ls.mode & 128)) {
+      if (t < T && !(ls.mode & kLagNoXx)) {
         const double* rowp = Dl + t * ldd;
         double s0 = xl[0], s1 = 0.0, s2 = 0.0, s3 = 0.0;
         if ((N & 3) == 0) {
@@ -928,64 +929,48 @@ bool lag_supported_nt(int nt) { return nt == 1 || nt == 15; }
 
 hipError_t lag_launch_gram(int NT, hipStream_t st, size_t lds, Dims d, const int* Tslot, LagSel ls,
                            ChainState cs, const double* iVdiag) {
-  const void* fn = nullptr;
+  auto go = [&](auto k) { return launch_k(k, dim3(d.nmat), dim3(512), lds, true, st, d, Tslot, ls, cs, iVdiag); };
   switch (NT) {
-    case 1: fn = (const void*)k_gram_chol_lag<1>; break;
-    case 15: fn = (const void*)k_gram_chol_lag<15>; break;
+    case 1: return go(k_gram_chol_lag<1>);
+    case 15: return go(k_gram_chol_lag<15>);
     default: return hipErrorInvalidValue;
   }
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  switch (NT) {
-    case 1: hipLaunchKernelGGL(k_gram_chol_lag<1>, dim3(d.nmat), dim3(512), lds, st, d, Tslot, ls, cs, iVdiag); break;
-    case 15: hipLaunchKernelGGL(k_gram_chol_lag<15>, dim3(d.nmat), dim3(512), lds, st, d, Tslot, ls, cs, iVdiag); break;
+}
+
+// f(the k_cta_solve_lag<NT, nmax, ro> instance), or `none` when none is compiled.  ro: row-owned substitutions
+// with LDS flag hand-offs (option solve_async = 1) or the barrier-stepped form (0); same arithmetic either way
+// (per-thread v_t and residual rows, per-tile substitution products, the X'v t-halves on threads 0..511)
+constexpr int sl_key(int NT, int nmax) { return 100 * NT + nmax; }  // nmax = n_bucket(N) < 100
+template <class R, class F>
+static R solve_instance(int NT, int nmax, bool ro, R none, F f) {
+  switch (sl_key(NT, nmax)) {
+    case sl_key(1, 8): return ro ? f(k_cta_solve_lag<1, 8, true>) : f(k_cta_solve_lag<1, 8, false>);
+    case sl_key(1, 20): return ro ? f(k_cta_solve_lag<1, 20, true>) : f(k_cta_solve_lag<1, 20, false>);
+    case sl_key(1, 32): return ro ? f(k_cta_solve_lag<1, 32, true>) : f(k_cta_solve_lag<1, 32, false>);
+    case sl_key(15, 8): return ro ? f(k_cta_solve_lag<15, 8, true>) : f(k_cta_solve_lag<15, 8, false>);
+    case sl_key(15, 20): return ro ? f(k_cta_solve_lag<15, 20, true>) : f(k_cta_solve_lag<15, 20, false>);
+    case sl_key(15, 32): return ro ? f(k_cta_solve_lag<15, 32, true>) : f(k_cta_solve_lag<15, 32, false>);
+    default: return none;
   }
-  return hipGetLastError();
-}
-
-// row-owned substitutions with LDS flag hand-offs (RO, option solve_async = 1) or the barrier-stepped
-// form (solve_async = 0).  Same arithmetic either way (per-thread v_t and residual rows, per-tile
-// substitution products, the X'v t-halves on threads 0..511).
-template <int NT, int NM, bool RO>
-static hipError_t solve_ro(hipStream_t st, size_t lds, Dims d, const int* Tslot, const double* iVb, XSel xs,
-                           LagSel ls, ChainState cs, RngArgs ra, SolveXch xc) {
-  hipError_t e = hipFuncSetAttribute((const void*)k_cta_solve_lag<NT, NM, 8, RO>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_cta_solve_lag<NT, NM, 8, RO>), dim3(d.B, xc.part ? 2 : 1), dim3(64 * 8), lds, st, d,
-                     Tslot, iVb, xs, ls, cs, ra, xc);
-  return hipGetLastError();
-}
-
-template <int NT, int NM, bool RO>
-static int solve_resident(size_t lds) {
-  const void* fn = (const void*)k_cta_solve_lag<NT, NM, 8, RO>;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * 8, lds) != hipSuccess) return 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  return per_cu * cus;
 }
 
 int lag_solve_resident(int NT, int nmax, size_t lds, int async) {
-#define SR_CASE(NT_, NM_)                                                                              \
-  if (NT == NT_ && nmax == NM_) return async ? solve_resident<NT_, NM_, true>(lds) : solve_resident<NT_, NM_, false>(lds);
-  SR_CASE(1, 8) SR_CASE(1, 20) SR_CASE(1, 32) SR_CASE(15, 8) SR_CASE(15, 20) SR_CASE(15, 32)
-#undef SR_CASE
-  return 0;
+  return solve_instance(NT, nmax, async != 0, 0, [&](auto k) {
+    int per_cu = 0, dev = 0, cus = 0;
+    if (raise_lds(k, lds) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k, kSlThreads, lds) != hipSuccess) return 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    return per_cu * cus;
+  });
 }
 
 hipError_t lag_launch_solve(int NT, int nmax, int async, hipStream_t st, size_t lds, Dims d, const int* Tslot,
                             const double* iVb, XSel xs, LagSel ls, ChainState cs, RngArgs ra, SolveXch xc) {
-#define SL_CASE(NT_, NM_)                                                                           \
-  if (NT == NT_ && nmax == NM_)                                                                     \
-    return async ? solve_ro<NT_, NM_, true>(st, lds, d, Tslot, iVb, xs, ls, cs, ra, xc)            \
-                 : solve_ro<NT_, NM_, false>(st, lds, d, Tslot, iVb, xs, ls, cs, ra, xc);
-  SL_CASE(1, 8) SL_CASE(1, 20) SL_CASE(1, 32) SL_CASE(15, 8) SL_CASE(15, 20) SL_CASE(15, 32)
-#undef SL_CASE
-  return hipErrorInvalidValue;
+  return solve_instance(NT, nmax, async != 0, hipErrorInvalidValue, [&](auto k) {
+    return launch_k(k, dim3(d.B, xc.part ? 2 : 1), dim3(kSlThreads), lds, true, st, d, Tslot, iVb, xs, ls, cs, ra, xc);
+  });
 }
 
 }  // namespace ccmm

@@ -23,6 +23,7 @@
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
+#include "ccmm_internal.h"
 #include "ccmm_post.h"
 
 namespace ccmm {
@@ -193,15 +194,13 @@ hipError_t post_summaries(hipStream_t st, int S, int n, const double* draws, dou
   auto at = [](double* p, size_t o) { return p ? p + o : nullptr; };
   for (size_t s0 = 0; s0 < (size_t)S; s0 += per) {
     const int Sc = (int)std::min(per, (size_t)S - s0);
-    hipLaunchKernelGGL(k_offsets, dim3((Sc + 256) / 256), dim3(256), 0, st, Sc, n, off);
-    PCHECK(hipGetLastError());
+    PCHECK(launch_k(k_offsets, dim3((Sc + 256) / 256), dim3(256), 0, false, st, Sc, n, off));
     PCHECK(rocprim::segmented_radix_sort_keys(tmp, tb, draws + s0 * n, sorted + s0 * n,
                                               (unsigned int)((size_t)Sc * n), (unsigned int)Sc, off, off + 1, 0, 64,
                                               st));
-    hipLaunchKernelGGL(k_post_stats, dim3(Sc), dim3(256), 0, st, Sc, n, sorted + s0 * n,
-                       realized ? realized + s0 : nullptr, nq, pct, at(mean, s0), at(median, s0), at(quant, s0),
-                       (size_t)S, at(sd, s0), at(crps, s0));
-    PCHECK(hipGetLastError());
+    PCHECK(launch_k(k_post_stats, dim3(Sc), dim3(256), 0, false, st, Sc, n, sorted + s0 * n,
+                    realized ? realized + s0 : nullptr, nq, pct, at(mean, s0), at(median, s0), at(quant, s0), (size_t)S,
+                    at(sd, s0), at(crps, s0)));
   }
   return hipSuccess;
 }
@@ -211,17 +210,15 @@ hipError_t post_gather_fcst(hipStream_t st, const double* src, int chain0, int C
                             double* dst) {
   const size_t total = (size_t)C * M * Nd * nr;
   const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_gather_fcst, dim3(blocks), dim3(256), 0, st, src, chain0, C, M, Nd, H, N, cap, rows,
-                     nr, cum, flo, fl, dst);
-  return hipGetLastError();
+  return launch_k(k_gather_fcst, dim3(blocks), dim3(256), 0, false, st, src, chain0, C, M, Nd, H, N, cap, rows, nr, cum,
+                  flo, fl, dst);
 }
 
 hipError_t post_gather_pai(hipStream_t st, const double* src, int chain0, int C, int M, int cap, int KN,
                            double* dst) {
   const size_t total = (size_t)C * M * KN;
   const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_gather_pai, dim3(blocks), dim3(256), 0, st, src, chain0, C, M, cap, KN, dst);
-  return hipGetLastError();
+  return launch_k(k_gather_pai, dim3(blocks), dim3(256), 0, false, st, src, chain0, C, M, cap, KN, dst);
 }
 
 }  // namespace ccmm

@@ -571,4 +571,13 @@ hipError_t launch_ps_apply(bool prop, hipStream_t st, int B, ElbDev e, PsDev ps,
   }
 }
 
+hipError_t launch_ps_first_store(hipStream_t st, int B, const double* first, const int* elbT, const int* slot,
+                                 double* out, int per, int Ns, int cap, int m) {
+  return launch_k(k_ps_first_store, dim3(B), dim3(256), 0, false, st, first, elbT, slot, out, per, Ns, cap, m);
+}
+
+hipError_t launch_ps_store(hipStream_t st, const int* flag, int* out, int B, int cap, int m) {
+  return launch_k(k_ps_store, dim3((B + 255) / 256), dim3(256), 0, false, st, flag, out, B, cap, m);
+}
+
 }  // namespace ccmm

@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * NW) void k_sv_part(Dims d, const int* __restri
   // the normals z_t (block t, row ln) are drawn grid-wide by k_sv_normals before this
   // kernel (independent work off the per-chain serial path) and read back from Zg
   auto zdraw = [&](int t) __attribute__((always_inline)) -> double {
-    if (mode & 32) return 0.0;  // timing ablation only
+    if (mode & kSvNoNormals) return 0.0;  // timing ablation only
     return real ? Zg[(size_t)t * NN + ln] : 0.0;
   };
   // C_t row (lane < NN) -> LDS, and its lower triangle packed by rows to HBM
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(64 * NW) void k_sv_part(Dims d, const int* __restri
   // ---------------------------------------------------------------- phase A: segments
   // per-wave LDS: myF[k*NN + r] fill column r of M_{t,left} (right-hand side of lane NN+r),
   // myD[r*NN + m] the left separator's accumulated -sum X2'X2 (row r)
-  for (int q = wave + NW * wg; q < ((mode & 1) ? 0 : P); q += NW * nwg) {
+  for (int q = wave + NW * wg; q < ((mode & kSvSkipA) ? 0 : P); q += NW * nwg) {
     const int first = (q == 0) ? 0 : sv_sep(q - 1, T, P) + 1;
     const int last = (q == P - 1) ? T : sv_sep(q, T, P) - 1;
     const bool hasL = q > 0, hasR = q < P - 1;
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(64 * NW) void k_sv_part(Dims d, const int* __restri
   __syncthreads();
 
   // ---------------------------------------------------------------- phase B: separators
-  if (wave == 0 && P > 1 && !(mode & 2)) {
+  if (wave == 0 && P > 1 && !(mode & kSvSkipBFwd)) {
     double cg[NN], sr[NN];
 #pragma unroll
     for (int m = 0; m < NN; ++m) cg[m] = 0.0;
@@ -639,7 +639,7 @@ __global__ __launch_bounds__(64 * NW) void k_sv_part(Dims d, const int* __restri
     read_factor(lr, lc, rd);
     sv_wave_sync();
   };
-  if (wave == 0 && P > 1 && !(mode & 4)) {
+  if (wave == 0 && P > 1 && !(mode & kSvSkipBBwd)) {
     for (int i = P - 2; i >= 0; --i) {
       const int sb = sv_sep(i, T, P);
       double lr[NN], lc[NN], rd;
@@ -662,11 +662,11 @@ __global__ __launch_bounds__(64 * NW) void k_sv_part(Dims d, const int* __restri
     }
   }
   __syncthreads();
-  for (int q = wave + NW * wg; q < ((mode & 8) ? 0 : P); q += NW * nwg) {
+  for (int q = wave + NW * wg; q < ((mode & kSvSkipC) ? 0 : P); q += NW * nwg) {
     const int first = (q == 0) ? 0 : sv_sep(q - 1, T, P) + 1;
     const int last = (q == P - 1) ? T : sv_sep(q, T, P) - 1;
     const bool hasL = q > 0, hasR = q < P - 1;
-    if (hasL && !(mode & 16)) {  // g_first = -Q x_left, g_{t+1} = Q C_t^-T C_t^-1 g_t
+    if (hasL && !(mode & kSvNoFill)) {  // g_first = -Q x_left, g_{t+1} = Q C_t^-T C_t^-1 g_t
       double g = 0.0;
 #pragma unroll
       for (int m = 0; m < NN; ++m) g = fma(-qrow[m], xsep[(q - 1) * NN + m], g);
@@ -723,7 +723,7 @@ __global__ __launch_bounds__(64 * NW) void k_sv_part(Dims d, const int* __restri
       if (hasL && lane < NN) acc += Gb[(size_t)t * NN + ln];
       double rv = (lane < NN) ? Wg[(size_t)t * NN + ln] + zdraw(t) : 0.0;
       double x;
-      if (mode & 64) {  // timing ablation only
+      if (mode & kSvNoBacksub) {  // timing ablation only
         x = rv - acc;
       } else {
         rv -= sv_fwd_d<NN>(acc, lr, rd, lane);
@@ -765,54 +765,56 @@ __global__ void k_sv_normals(Dims d, const int* __restrict__ Tslot, ChainState c
   gbuf[(size_t)(d.B + c) * (d.TP + 1) * NN + (size_t)t * NN + i] = rng.normal(CCMM_RNG_SVZ, (uint32_t)(i + n * t));
 }
 
+// what every launch of one sv_launch_part call shares
+struct SvLaunch {
+  hipStream_t st;
+  Dims d;
+  const int* Tslot;
+  const double *V0inv, *V0invm;
+  ChainState cs;
+  RngArgs ra;
+  double *sep, *gbuf;
+  int mode, nwg;
+};
+
 template <int NN, int NW, bool PACK, bool MF>
-static hipError_t sv_launch_k(hipStream_t st, Dims d, const int* Tslot, const double* V0inv,
-                              const double* V0invm, ChainState cs, RngArgs ra, double* sep, double* gbuf,
-                              int mode, int nwg) {
+static hipError_t sv_launch_k(const SvLaunch& a, int mode) {
+  const Dims& d = a.d;
   const size_t lds = (size_t)(2 * NN * NN + kSvMaxSeg * NN + NW * sv_wave_lds(NN)) * sizeof(double);
-  hipError_t e = hipFuncSetAttribute((const void*)k_sv_part<NN, NW, PACK, MF>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const auto part = k_sv_part<NN, NW, PACK, MF>;
+  auto go = [&](dim3 grid, int m) {
+    return launch_k(part, grid, dim3(64 * NW), lds, false, a.st, d, a.Tslot, a.V0inv, a.V0invm, a.cs, a.ra, a.sep, a.gbuf,
+                    m, a.nwg);
+  };
+  hipError_t e = raise_lds(part, lds);  // once, for every launch of the kernel below
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_sv_normals, dim3(((d.TP + 1) * d.N + 255) / 256, d.B), dim3(256), 0, st, d, Tslot, cs, ra,
-                     gbuf, NN);
+  e = launch_k(k_sv_normals, dim3(((d.TP + 1) * d.N + 255) / 256, d.B), dim3(256), 0, false, a.st, d, a.Tslot, a.cs, a.ra,
+               a.gbuf, NN);
+  if (e != hipSuccess) return e;
   // small batches (B <= 128, e.g. the OOS chains of one vintage): the segments of phases A and C
   // are spread over nwg = 2 (or 4) workgroups per chain (16 segments = one per wave), as two
   // launches: phase A, then phases B + C, in which every workgroup of the chain redoes the serial
   // separator pass (identical values and stores) instead of a third launch; same draws
-  if (nwg == 1) {
-    hipLaunchKernelGGL((k_sv_part<NN, NW, PACK, MF>), dim3(d.B), dim3(64 * NW), lds, st, d, Tslot, V0inv, V0invm,
-                       cs, ra, sep, gbuf, mode, 1);
-  } else {
-    hipLaunchKernelGGL((k_sv_part<NN, NW, PACK, MF>), dim3(d.B, nwg), dim3(64 * NW), lds, st, d, Tslot, V0inv,
-                       V0invm, cs, ra, sep, gbuf, mode | 2 | 4 | 8, nwg);
-    hipLaunchKernelGGL((k_sv_part<NN, NW, PACK, MF>), dim3(d.B, nwg), dim3(64 * NW), lds, st, d, Tslot, V0inv,
-                       V0invm, cs, ra, sep, gbuf, mode | 1, nwg);
-  }
-  return hipGetLastError();
+  if (a.nwg == 1) return go(dim3(d.B), mode);
+  e = go(dim3(d.B, a.nwg), mode | kSvSkipBFwd | kSvSkipBBwd | kSvSkipC);
+  return e != hipSuccess ? e : go(dim3(d.B, a.nwg), mode | kSvSkipA);
 }
 
-// NN = 20: phase A's block products on MFMA unless option sv_mfma = 0 (mode bit 256 here): a different
+// NN = 20: phase A's block products on MFMA unless option sv_mfma = 0 (kSvFma here): a different
 // accumulation order than the FMA pass, so the two forms agree to rounding, not bit for bit
 template <int NN, int NW, bool PACK>
-static hipError_t sv_launch_one_(hipStream_t st, Dims d, const int* Tslot, const double* V0inv,
-                                const double* V0invm, ChainState cs, RngArgs ra, double* sep, double* gbuf,
-                                int mode, int nwg) {
-  if constexpr (NN == 20) {
-    if (mode & 256)
-      return sv_launch_k<NN, NW, PACK, false>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode & ~256, nwg);
-  }
-  return sv_launch_k<NN, NW, PACK, true>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
+static hipError_t sv_launch_form(const SvLaunch& a) {
+  if constexpr (NN == 20)
+    if (a.mode & kSvFma) return sv_launch_k<NN, NW, PACK, false>(a, a.mode & ~kSvFma);
+  return sv_launch_k<NN, NW, PACK, true>(a, a.mode);
 }
 
 // block factors stored as packed lower triangles (default: 0.55x the factor traffic of full rows,
 // and no register spills at NN = 20; measured 2.16 vs 2.19 ms at N = 20, B = 256 since the factor
-// leaves LDS by coalesced stores) or as full rows (mode bit 128, for comparison); same draws
+// leaves LDS by coalesced stores) or as full rows (kSvFullRows, for comparison); same draws
 template <int NN, int NW>
-static hipError_t sv_launch_one(hipStream_t st, Dims d, const int* Tslot, const double* V0inv,
-                                const double* V0invm, ChainState cs, RngArgs ra, double* sep, double* gbuf,
-                                int mode, int nwg) {
-  if (mode & 128) return sv_launch_one_<NN, NW, false>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-  return sv_launch_one_<NN, NW, true>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
+static hipError_t sv_launch_one(const SvLaunch& a) {
+  return (a.mode & kSvFullRows) ? sv_launch_form<NN, NW, false>(a) : sv_launch_form<NN, NW, true>(a);
 }
 
 // Workgroups per chain: 1 from B = 129 (the chip is full), 2 of 8 waves down to B = 33, and at
@@ -825,25 +827,18 @@ hipError_t sv_launch_part(int N, hipStream_t st, Dims d, const int* Tslot, const
   const int nb = sv_bucket(N);
   int nwg = d.B <= 32 && nb <= 20 ? 4 : (d.B <= 128 ? 2 : 1);
   if (nwg_opt > 0) nwg = nwg_opt >= 4 && nb <= 20 ? 4 : std::max(1, std::min(2, nwg_opt));
-  if (!mfma) mode |= 256;
-  if (nwg == 4) {
-    switch (nb) {
-      case 4: return sv_launch_one<4, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, 4);
-      case 8: return sv_launch_one<8, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, 4);
-      case 12: return sv_launch_one<12, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, 4);
-      case 16: return sv_launch_one<16, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, 4);
-      default: return sv_launch_one<20, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, 4);
-    }
-  }
+  if (!mfma) mode |= kSvFma;
+  const SvLaunch a{st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg};
+  const bool w4 = nwg == 4;  // four waves per workgroup (nb <= 20 only), else eight
   switch (nb) {
-    case 4: return sv_launch_one<4, 8>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    case 8: return sv_launch_one<8, 8>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    case 12: return sv_launch_one<12, 8>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    case 16: return sv_launch_one<16, 8>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    case 20: return sv_launch_one<20, 8>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    case 24: return sv_launch_one<24, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    case 28: return sv_launch_one<28, 4>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);
-    default: return sv_launch_one<32, 2>(st, d, Tslot, V0inv, V0invm, cs, ra, sep, gbuf, mode, nwg);  // LDS
+    case 4: return w4 ? sv_launch_one<4, 4>(a) : sv_launch_one<4, 8>(a);
+    case 8: return w4 ? sv_launch_one<8, 4>(a) : sv_launch_one<8, 8>(a);
+    case 12: return w4 ? sv_launch_one<12, 4>(a) : sv_launch_one<12, 8>(a);
+    case 16: return w4 ? sv_launch_one<16, 4>(a) : sv_launch_one<16, 8>(a);
+    case 20: return w4 ? sv_launch_one<20, 4>(a) : sv_launch_one<20, 8>(a);
+    case 24: return sv_launch_one<24, 4>(a);
+    case 28: return sv_launch_one<28, 4>(a);
+    default: return sv_launch_one<32, 2>(a);  // LDS
   }
 }
 

@@ -1,8 +1,9 @@
 // Host-visible layouts, LDS sizes, launch decisions and host launchers of the per-sweep kernels of the
 // generic (small-N) path: residuals, CTA weights, the A-step, the KSC indicators, PHI, the draw store and the
 // drop-in helpers (ccmm_kernels.hip), the fused Gram + Cholesky (ccmm_gram_chol.hip) and the per-chain solve
-// (ccmm_cta_solve.hip).  Each file is its own translation unit and launches its own templated kernels; the
-// size and decision functions make no HIP call (tests/launch_plans_main.cpp prints them on the host).
+// (ccmm_cta_solve.hip).  Each file is its own translation unit and launches every kernel it defines: the host units
+// see launchers only, no kernel.  The size and decision functions make no HIP call (tests/launch_plans_main.cpp
+// prints them on the host).
 #pragma once
 #include <algorithm>
 
@@ -44,9 +45,11 @@ struct GcArgs {
   double* L;         // KP x KP output
   double* rd;        // KP output
   int T, TP, KP;
-  int mode;  // timing-only ablation (CCMM_GC_MODE): 1 no SYRK, 2 no Cholesky, 4 no trailing
-             // update, 8 no panel solve, 16 no diagonal factor
+  int mode;  // kGc* bits below; 0 in production
 };
+// bits of GcArgs::mode: none selects what is computed; all are timing-only (CCMM_GC_MODE, ablation build; results
+// invalid): no SYRK, no Cholesky, no trailing update, no panel solve, no diagonal factor
+constexpr int kGcNoSyrk = 1, kGcNoChol = 2, kGcNoTrailing = 4, kGcNoPanel = 8, kGcNoDiag = 16;
 
 // LDS of k_gram_chol<NT>: max(SYRK stage Z0 | Z1 [kGcTC x gc_ldz(NT)], factor stage Dg | Pn[NT] [16 x kGcLdp])
 inline size_t gram_chol_lds_bytes(int NT) {
@@ -105,29 +108,36 @@ inline AstepPlan astep_plan(int N, int TP) {
 hipError_t launch_astep(bool serial, hipStream_t st, Dims d, const int* Tslot, ChainState cs, RngArgs ra,
                         double logy2offset, const int* gtab);
 
-// LDS of k_phi: Lpost | Rz | Sq | Ph [N x (N + 1) each] | eta [N x (TP + 1)] (stage_eta bit 0), the region wide
-// enough for Z [N x (TP + dPHI)] after it (bit 1), when they fit
+// LDS of k_phi: Lpost | Rz | Sq | Ph [N x (N + 1) each] | eta [N x (TP + 1)] (kPhiStageEta), the region wide
+// enough for Z [N x (TP + dPHI)] after it (kPhiStageZ), when they fit
 struct PhiPlan {
   size_t lds;
   int stage_eta;
 };
+// bits of stage_eta: what k_phi reads from LDS (the same products in the same order); none is timing-only
+constexpr int kPhiStageEta = 1;  // eta staged with row stride TP + 1
+constexpr int kPhiStageZ = 2;    // Z follows eta into the same region
 inline PhiPlan phi_plan(int N, int TP, int dPHI) {
   const size_t lds = (size_t)(4 * N * (N + 1)) * sizeof(double);
   const size_t staged = lds + (size_t)N * (TP + 1) * sizeof(double);
   const size_t staged_z = lds + (size_t)N * std::max(TP + 1, TP + dPHI) * sizeof(double);
-  return staged_z <= kLdsCu ? PhiPlan{staged_z, 3} : (staged <= kLdsCu ? PhiPlan{staged, 1} : PhiPlan{lds, 0});
+  return staged_z <= kLdsCu ? PhiPlan{staged_z, kPhiStageEta | kPhiStageZ}
+                            : (staged <= kLdsCu ? PhiPlan{staged, kPhiStageEta} : PhiPlan{lds, 0});
 }
 hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs);
 
-__global__ void k_sv_mix(Dims d, const int* __restrict__ Tslot, ChainState cs, RngArgs ra);
-__global__ void k_phi_gen(Dims d, const int* __restrict__ Tslot, int dPHI, ChainState cs, RngArgs ra);
-__global__ void k_store(Dims d, ChainState cs, Store st);
-__global__ void k_pai_moments(const double* __restrict__ sPAI, int cap, int m0, int m1, int per, int B,
-                              double* __restrict__ sum, double* __restrict__ sumsq);
-__global__ void k_truncnorm(int n, const double* mu, const double* sig, double elb, const double* u, double* out,
-                            uint8_t* flags);
-__global__ void k_rng_normals(RngArgs ra, int c, int block, int n, double* __restrict__ out);
-__global__ void k_mfma_selftest(const double* A, const double* B, double* D);
-__global__ void k_mfma_selftest_acc(const double* A, const double* B, const double* C, double* D, int nprobe);
+// the untemplated kernels: one thread per element (k_store: a fixed 64 x B grid; the self-tests: one wave per probe)
+hipError_t launch_sv_mix(hipStream_t st, Dims d, const int* Tslot, ChainState cs, RngArgs ra);
+hipError_t launch_phi_gen(hipStream_t st, Dims d, const int* Tslot, int dPHI, ChainState cs, RngArgs ra);
+hipError_t launch_store(hipStream_t st, Dims d, ChainState cs, Store s);
+// sums and sums of squares of the stored PAI draws m0 <= m < m1, `per` entries of each of B chains
+hipError_t launch_pai_moments(hipStream_t st, const double* sPAI, int cap, int m0, int m1, int per, int B, double* sum,
+                              double* sumsq);
+hipError_t launch_truncnorm(hipStream_t st, int n, const double* mu, const double* sig, double elb, const double* u,
+                            double* out, uint8_t* flags);
+hipError_t launch_rng_normals(hipStream_t st, RngArgs ra, int c, int block, int n, double* out);
+hipError_t launch_mfma_selftest(hipStream_t st, const double* A, const double* B, double* D);
+hipError_t launch_mfma_selftest_acc(hipStream_t st, const double* A, const double* B, const double* C, double* D,
+                                    int nprobe);
 
 }  // namespace ccmm

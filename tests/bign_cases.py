@@ -14,7 +14,7 @@ not).  Each table entry names the edge it sits on:
   half              the 64-lane halves of wave_trsv_* (lane + 64 < n) and of the SV backward pass (a = 64 h + gj)
   127               the row clamp min(., 127) of the 4 x 4 tiles of wg_gram and wg_chol
   stage             the 256-month staging chunks of the twin (kStageMonths) and the three-way choice of
-                    big_launch_cta: staged, read from L2 because KP > kStageMaxKP, read from L2 because of LDS
+                    big_launch_solve: staged, read from L2 because KP > kStageMaxKP, read from L2 because of LDS
 """
 import functools
 
@@ -59,7 +59,7 @@ SV = [(33, 1), (33, 3), (33, 31), (33, 32), (33, 33),  # NB = 3 with one row in 
       (127, 4), (128, 4)]                              # NB = 8, 15 and 16 rows in the last block
 SV_MULTI = (65, 5, 3)  # (N, T, B): three distinct chains
 
-# ---- linear sweeps (N, p, T), B = 2, T > N: (edge, branch of big_launch_cta) ------------------------------------
+# ---- linear sweeps (N, p, T), B = 2, T > N: (edge, branch of big_launch_solve) ------------------------------------
 SWEEPS = {
     (33, 1, 256): "staged",   # one 256-month staging chunk (TP = 256); int4: 33 = 8 * 4 + 1
     (33, 1, 257): "staged",   # two staging chunks (TP = 288), the second with 32 months

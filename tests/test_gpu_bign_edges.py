@@ -123,7 +123,7 @@ def test_sv_multi_chain(ctx):
 @pytest.mark.parametrize("N,p,T", list(bc.SWEEPS))
 def test_sweep_edges(pkg, ctx, N, p, T):
     """One CRN sweep of two chains: the large coefficient block with the lag twin, then every bign block."""
-    assert bc.solve_plan(N, p, T)[0] == bc.SWEEPS[N, p, T]  # the branch of big_launch_cta the case is there for
+    assert bc.solve_plan(N, p, T)[0] == bc.SWEEPS[N, p, T]  # the branch of big_launch_solve the case is there for
     su, sts, crns = bc.sweep_inputs(N, p, T)
     ref = bc.sweep_reference(N, p, T)
     B = len(sts)
