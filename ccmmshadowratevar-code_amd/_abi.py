@@ -137,6 +137,8 @@ _SIGS = {
     "ccmm_chains_fcst_stored": (C.c_int, [C.c_void_p]),
     "ccmm_chains_set_fcst_censor": (C.c_int, [C.c_void_p, _u8p]),
     "ccmm_chains_get_fcst": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ccmm_chains_set_irf1": (C.c_int, [C.c_void_p, C.c_double, _u8p]),
+    "ccmm_chains_get_irf1": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ccmm_chains_set_elb_model": (C.c_int, [C.c_void_p, _ip, _u8p]),
     "ccmm_chains_set_elb_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p]),
     "ccmm_chains_get_shadowrate": (C.c_int, [C.c_void_p, _dp]),
@@ -176,6 +178,9 @@ _SIGS = {
     "ccmm_fcst": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
                             _dp, _dp, _dp, _dp, _u8p, C.c_double, _dp, _dp, C.c_uint64,
                             C.c_int, _dp, _dp, _dp, _dp, _ip]),
+    "ccmm_fcst_irf1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                 _dp, _dp, _dp, _dp, _u8p, C.c_double, _dp, _dp, C.c_uint64,
+                                 C.c_int, _dp, _dp, _dp, _dp, _ip, C.c_double, _dp, _dp]),
     "ccmm_run_batch": (C.c_int, [C.c_void_p, C.POINTER(BatchConfig), C.c_int, C.POINTER(Vintage),
                                  C.POINTER(BatchOut)]),
     "ccmm_psrf": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp]),
@@ -565,12 +570,27 @@ class Context:
         Returns fcstY, fcstYcensor (N x H x Nd x B), yhat (N x H x B),
         scores (4 x Nd x B: logscore, ELB logscore, X logscore, I logscore), status (B).
         """
+        return self._fcst(None, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
+                          fcstNhorizons, Ndraws, svz, z, seed, sweep)
+
+    def fcst_irf1(self, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
+                  fcstNhorizons, Ndraws, IRF1scale, svz=None, z=None, seed=0, sweep=0):
+        """``fcst`` with the doIRF1 simulations of mcmcVARshadowrate.m:588-605 (ccmm_fcst_irf1): the linear
+        recursion twice more on the draw's shocks, the structural shock of variable 1 (index 0) at horizon 1
+        replaced by +IRF1scale and by -IRF1scale.  Returns the five outputs of ``fcst``, then fcstY1plus and
+        fcstY1minus (N x H x Nd x B, as simulated: neither floored nor cumulated)."""
+        return self._fcst(float(IRF1scale), PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
+                          fcstNhorizons, Ndraws, svz, z, seed, sweep)
+
+    def _fcst(self, irf1scale, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
+              fcstNhorizons, Ndraws, svz, z, seed, sweep):
+        what = "ccmm_fcst" if irf1scale is None else "ccmm_fcst_irf1"
         PAI = _f(PAI)
         K, N = PAI.shape[:2]
         B = PAI.shape[2] if PAI.ndim == 3 else 1
         p = (K - 1) // N
         if K != N * p + 1:
-            raise ValueError("ccmm_fcst: K must equal N*p + 1 (mcmcVAR.m:108-115)")
+            raise ValueError(f"{what}: K must equal N*p + 1 (mcmcVAR.m:108-115)")
         H, Nd = int(fcstNhorizons), int(Ndraws)
         fY = np.zeros((N, H, Nd, B), order="F")
         fYc = np.zeros((N, H, Nd, B), order="F")
@@ -579,15 +599,21 @@ class Context:
         st = np.zeros(B, dtype=np.int32)
         mask = np.ascontiguousarray(np.asarray(ndxYields, bool).astype(np.uint8))
         crn = svz is not None
-        rc = self.lib.ccmm_fcst(self.handle, B, N, p, H, Nd, _ptr(PAI), _ptr(_f(invA)),
-                                _ptr(_f(logSV0)), _ptr(_f(sqrtPHI)), _ptr(_f(Xjumpoff)),
-                                _ptr(_f(yrealized)), _ptr(mask, _u8p), float(ELBbound),
-                                _ptr(_f(svz)) if crn else None, _ptr(_f(z)) if crn else None,
-                                int(seed), int(sweep), _ptr(fY), _ptr(fYc), _ptr(yhat),
-                                _ptr(sc), _ptr(st, _ip))
+        args = [self.handle, B, N, p, H, Nd, _ptr(PAI), _ptr(_f(invA)),
+                _ptr(_f(logSV0)), _ptr(_f(sqrtPHI)), _ptr(_f(Xjumpoff)),
+                _ptr(_f(yrealized)), _ptr(mask, _u8p), float(ELBbound),
+                _ptr(_f(svz)) if crn else None, _ptr(_f(z)) if crn else None,
+                int(seed), int(sweep), _ptr(fY), _ptr(fYc), _ptr(yhat),
+                _ptr(sc), _ptr(st, _ip)]
+        out = [fY, fYc, yhat, sc, st]
+        if irf1scale is None:
+            rc = self.lib.ccmm_fcst(*args)
+        else:
+            out += [np.zeros((N, H, Nd, B), order="F"), np.zeros((N, H, Nd, B), order="F")]
+            rc = self.lib.ccmm_fcst_irf1(*args, irf1scale, _ptr(out[5]), _ptr(out[6]))
         if rc != CCMM_WARN_MVNCDF:
-            _check(rc, "ccmm_fcst")
-        return fY, fYc, yhat, sc, st
+            _check(rc, what)
+        return tuple(out)
 
     def draw_trunc_normal_batch(self, mu, sig, elb, u):
         mu = _f(mu).ravel(order="F")
@@ -1079,6 +1105,40 @@ class Chains:
         if rc != CCMM_WARN_MVNCDF:
             _check(rc, "ccmm_chains_get_fcst")
         out["warn_mvncdf"] = rc == CCMM_WARN_MVNCDF
+        return out
+
+    def set_irf1(self, scale, cumcode=None):
+        """doIRF1 (ccmm_chains_set_irf1; after set_fcst): every kept draw's predictive simulation twice more on
+        the same shocks, the structural shock of variable 1 (index 0) at horizon 1 replaced by +scale and by
+        -scale.  cumcode (IRFcumcode): 0-based indices or a bool vector of the rows cumulated over the horizons."""
+        m = None
+        if cumcode is not None:
+            cc = np.asarray(cumcode)
+            if cc.dtype != bool:
+                idx, cc = cc.astype(int).ravel(), np.zeros(self.N, bool)
+                cc[idx] = True
+            if cc.shape != (self.N,):
+                raise ValueError("set_irf1: cumcode must have N entries")
+            m = np.ascontiguousarray(cc, dtype=np.uint8)
+        _check(self.lib.ccmm_chains_set_irf1(self.handle, float(scale), None if m is None else m.ctypes.data_as(_u8p)),
+               "ccmm_chains_set_irf1")
+
+    def get_irf1(self, paths=False):
+        """IRF1 records of the kept draws so far (not reset: get_fcst resets them with its own, so call this
+        first): drawsPlus / drawsMinus N x H x M x B (IRF1drawsPlus / Minus), y1sumPlus / y1sumMinus N x H x B
+        (sums of the floored, cumulated plus / minus paths over the M x Nd draws), and with ``paths`` the paths
+        as simulated, pathsPlus / pathsMinus N x H x Nd x M x B."""
+        M = self.fcst_stored()
+        N, H, Nd, B = self.N, self.fH, self.fNd, self.B
+        out = dict(M=M, drawsPlus=np.zeros((N, H, M, B), order="F"), drawsMinus=np.zeros((N, H, M, B), order="F"),
+                   y1sumPlus=np.zeros((N, H, B), order="F"), y1sumMinus=np.zeros((N, H, B), order="F"))
+        if paths:
+            out["pathsPlus"] = np.zeros((N, H, Nd, M, B), order="F")
+            out["pathsMinus"] = np.zeros((N, H, Nd, M, B), order="F")
+        _check(self.lib.ccmm_chains_get_irf1(self.handle, _ptr(out["drawsPlus"]), _ptr(out["drawsMinus"]),
+                                             _ptr(out["y1sumPlus"]), _ptr(out["y1sumMinus"]),
+                                             _ptr(out.get("pathsPlus")), _ptr(out.get("pathsMinus"))),
+               "ccmm_chains_get_irf1")
         return out
 
     # ------------------------------------------------ block-hybrid shadow-rate model

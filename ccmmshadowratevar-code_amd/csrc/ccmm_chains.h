@@ -148,6 +148,14 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   std::vector<bool> have_fcst_slot;
   DBuf<double> fYreal, fXj, fY, fYc, fYhat, fSc, fYsum, fYcsum, fYhatsum, fScStore, fPaths, fPathsC, fSv1;
   DBuf<int> fStatus;
+  // doIRF1 (ccmm_chains_set_irf1): the plus / minus simulations of every kept draw beside its predictive density.
+  // fY1p / fY1m: the kept draw's raw paths; fIrfP / fIrfM: [B][cap][H][N] IRF1drawsPlus / Minus; fY1sumP / M:
+  // [B][H][N] running sums of the floored (and cumulated) paths; fIrfTmp: k_fcst_irf_accum's scratch;
+  // fPathsP / M: the raw paths of every kept draw (keep_paths)
+  bool have_irf = false;
+  double irfScale = 0.0;
+  DBuf<uint8_t> fIrfCum;
+  DBuf<double> fY1p, fY1m, fIrfP, fIrfM, fY1sumP, fY1sumM, fIrfTmp, fPathsP, fPathsM;
   // the predictive density of a kept sweep on the auxiliary stream (option fcst_overlap, N <= 32): it reads
   // the sweep's PAI, invA, h, sqrtPHI and the chain's Y, which the next sweep first rewrites in its CTA
   // solve (PAI), so it runs beside the next sweep's residual, weights and Gram + Cholesky; join_fcst()
@@ -302,6 +310,7 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
 
   // ================================================================ ccmm_chains_fcst.hip
   void set_fcst(int H, int Nd, const uint8_t* ndxYields, int keep);
+  void set_irf1(double scale, const uint8_t* cumcode);
   void reset_fcst();
   void run_fcst(const ccmm::RngArgs& ra);
   void join_fcst();

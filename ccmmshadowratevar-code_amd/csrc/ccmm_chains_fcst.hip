@@ -55,8 +55,37 @@ void ccmm_chains::set_fcst(int H, int Nd, const uint8_t* ndxYields, int keep) {
           "forecast state does not fit LDS");
   fSv1.alloc(B * Nd * N);
   have_fcst = true;
+  have_irf = false;  // (its buffers follow H, Nd and keep_paths: ccmm_chains_set_irf1 comes after this call)
   reset_fcst();
   layout_crn();
+}
+
+void ccmm_chains::set_irf1(double scale, const uint8_t* cumcode) {
+  const int N = cfg.N, p = cfg.p, bhf = hybrid ? 2 : (fcst_bh ? 1 : 0);
+  // (the LDS form's plan, as set_fcst: no register-path shape is larger)
+  require(fcst_irf_lds_doubles(N, cfg.K, p, fcst_irf_chunk(N, cfg.K, p, fH, false, bhf), false, bhf) * sizeof(double) <=
+              kLdsCu,
+          "forecast state does not fit LDS");
+  const size_t B = cfg.B, HN = (size_t)fH * N, cap = cfg.store_capacity;
+  std::vector<uint8_t> cc(N, 0);
+  if (cumcode)
+    for (int i = 0; i < N; ++i) cc[i] = cumcode[i] ? 1 : 0;
+  fIrfCum.alloc(N);
+  HIPCHECK(hipMemcpy(fIrfCum.p, cc.data(), N, hipMemcpyHostToDevice));
+  fY1p.alloc(B * fNd * HN);
+  fY1m.alloc(B * fNd * HN);
+  fIrfP.alloc(B * cap * HN);
+  fIrfM.alloc(B * cap * HN);
+  fY1sumP.alloc(B * HN);
+  fY1sumM.alloc(B * HN);
+  fIrfTmp.alloc(B * 2 * HN);
+  if (fKeep) {
+    fPathsP.alloc(B * cap * fNd * HN);
+    fPathsM.alloc(B * cap * fNd * HN);
+  }
+  irfScale = scale;
+  have_irf = true;
+  reset_fcst();
 }
 void ccmm_chains::reset_fcst() {
   const size_t HN = (size_t)fH * cfg.N, B = cfg.B;
@@ -64,6 +93,10 @@ void ccmm_chains::reset_fcst() {
   HIPCHECK(hipMemsetAsync(fYcsum.p, 0, B * HN * sizeof(double), ctx->stream));
   HIPCHECK(hipMemsetAsync(fYhatsum.p, 0, B * HN * sizeof(double), ctx->stream));
   HIPCHECK(hipMemsetAsync(fStatus.p, 0, B * sizeof(int), ctx->stream));
+  if (have_irf) {
+    HIPCHECK(hipMemsetAsync(fY1sumP.p, 0, B * HN * sizeof(double), ctx->stream));
+    HIPCHECK(hipMemsetAsync(fY1sumM.p, 0, B * HN * sizeof(double), ctx->stream));
+  }
   HIPCHECK(hipStreamSynchronize(ctx->stream));
   fstored = 0;
 }
@@ -106,6 +139,11 @@ void ccmm_chains::run_fcst(const RngArgs& ra) {
   }
   a.seed = cfg.seed; a.sweep = ra.sweep; a.ids = ra.ids;
   a.fY = fY.p; a.fYc = fYc.p; a.yhat = fYhat.p; a.scores = fSc.p; a.status = fStatus.p;
+  if (have_irf) {
+    a.irfScale = irfScale;
+    a.fY1p = fY1p.p;
+    a.fY1m = fY1m.p;
+  }
   a.gl = gl_nodes();
   a.mode = env_ablation("CCMM_FCST_MODE", 0);  // timing-only (kFcstNoScores, kFcstNoHorizons)
   const XSel xs = xsel();
@@ -114,6 +152,9 @@ void ccmm_chains::run_fcst(const RngArgs& ra) {
     HIPCHECK(launch_fcst(fst, a, fSv1.p, opt[OPT_FCST_REG] != 0));
     HIPCHECK(launch_fcst_accum(fst, a, cfg.store_capacity, fstored, (fcst_bh || hybrid) ? nullptr : fYhat.p, fYsum.p,
                                fYcsum.p, fYhatsum.p, fScStore.p, fKeep ? fPaths.p : nullptr, fKeep ? fPathsC.p : nullptr));
+    if (have_irf)
+      HIPCHECK(launch_fcst_irf_accum(fst, a, cfg.store_capacity, fstored, fIrfCum.p, fIrfP.p, fIrfM.p, fY1sumP.p,
+                                     fY1sumM.p, fIrfTmp.p, fKeep ? fPathsP.p : nullptr, fKeep ? fPathsM.p : nullptr));
   }, fst);
   ++fstored;
   if (overlap) {
@@ -253,6 +294,47 @@ int ccmm_chains_set_fcst_censor(ccmm_chains* ch, const uint8_t* floor_in_recursi
   });
 }
 
+int ccmm_chains_set_irf1(ccmm_chains* ch, double scale, const uint8_t* cumcode) {
+  if (ch && !ch->have_fcst) {
+    set_last_error("ccmm_chains_set_fcst must be called before set_irf1");
+    return CCMM_ERR_STATE;
+  }
+  return guarded([&] {
+    require(ch != nullptr, "null argument");
+    require(std::isfinite(scale), "IRF1scale must be finite");
+    HIPCHECK(hipSetDevice(ch->ctx->device));
+    HIPCHECK(hipStreamSynchronize(ch->ctx->stream));
+    ch->set_irf1(scale, cumcode);
+    return 0;
+  });
+}
+
+int ccmm_chains_get_irf1(ccmm_chains* ch, double* drawsPlus, double* drawsMinus, double* y1sumPlus,
+                         double* y1sumMinus, double* pathsPlus, double* pathsMinus) {
+  return guarded([&] {
+    require(ch != nullptr, "null argument");
+    require(ch->have_fcst && ch->have_irf, "ccmm_chains_set_irf1 was not called");
+    HIPCHECK(hipSetDevice(ch->ctx->device));
+    HIPCHECK(hipStreamSynchronize(ch->ctx->stream));
+    const size_t B = ch->cfg.B, Nd = ch->fNd, cap = ch->cfg.store_capacity, M = ch->fstored;
+    const size_t HN = (size_t)ch->fH * ch->cfg.N;
+    // device [c][m][..] with cap records per chain -> M records per chain, the device order inside a record
+    auto fetch = [&](const DBuf<double>& src, double* dst, size_t rec) {
+      if (!dst || !M) return;
+      for (size_t c = 0; c < B; ++c)
+        HIPCHECK(hipMemcpy(dst + c * M * rec, src.p + c * cap * rec, M * rec * sizeof(double), hipMemcpyDeviceToHost));
+    };
+    fetch(ch->fIrfP, drawsPlus, HN);
+    fetch(ch->fIrfM, drawsMinus, HN);
+    if (y1sumPlus) HIPCHECK(hipMemcpy(y1sumPlus, ch->fY1sumP.p, B * HN * sizeof(double), hipMemcpyDeviceToHost));
+    if (y1sumMinus) HIPCHECK(hipMemcpy(y1sumMinus, ch->fY1sumM.p, B * HN * sizeof(double), hipMemcpyDeviceToHost));
+    if ((pathsPlus || pathsMinus) && M) require(ch->fKeep != 0, "paths were not kept (keep_paths = 0)");
+    fetch(ch->fPathsP, pathsPlus, Nd * HN);
+    fetch(ch->fPathsM, pathsMinus, Nd * HN);
+    return 0;
+  });
+}
+
 int ccmm_chains_fcst_stored(const ccmm_chains* ch) { return ch && ch->have_fcst ? ch->fstored : -1; }
 
 int ccmm_chains_get_fcst(ccmm_chains* ch, double* scores, double* fYsum, double* fYcsum,
@@ -340,12 +422,15 @@ int ccmm_chains_summaries_floor(ccmm_chains* ch, int source, int slot, const uin
   });
 }
 
-int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI,
-              const double* invA, const double* logSV0, const double* sqrtPHI,
-              const double* Xjumpoff, const double* yrealized, const uint8_t* ndxYields,
-              double elb, const double* svz, const double* z, uint64_t seed, int sweep,
-              double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status) {
+// ccmm_fcst (irf = false) and ccmm_fcst_irf1
+static int fcst_dropin(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI, const double* invA,
+                       const double* logSV0, const double* sqrtPHI, const double* Xjumpoff, const double* yrealized,
+                       const uint8_t* ndxYields, double elb, const double* svz, const double* z, uint64_t seed,
+                       int sweep, double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status,
+                       bool irf, double irf1scale, double* fcstY1plus, double* fcstY1minus) {
   return guarded([&] {
+    require(!irf || (fcstY1plus && fcstY1minus), "null argument");
+    require(!irf || std::isfinite(irf1scale), "IRF1scale must be finite");
     require(ctx && PAI && invA && logSV0 && sqrtPHI && Xjumpoff && yrealized && ndxYields &&
                 fcstY && fcstYcensor && yhat && scores,
             "null argument");
@@ -360,11 +445,13 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
     // largest, N = 21, p = 12 at hc = 1, is 253 * 21 + 2 * 441 + 2 * 252 + 63 = 6762 doubles, 53 KB)
     require(fcst_paths_lds_doubles(N, K, p, fcst_chunk(N, K, p, H)) * sizeof(double) <= kLdsCu,
             "forecast state does not fit LDS");
+    require(!irf || fcst_irf_lds_doubles(N, K, p, fcst_irf_chunk(N, K, p, H, false, 0), false, 0) * sizeof(double) <= kLdsCu,
+            "forecast state does not fit LDS");
     auto up = [&](DBuf<double>& d, const double* h, size_t n) {
       d.alloc(n);
       HIPCHECK(hipMemcpyAsync(d.p, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     };
-    DBuf<double> dPAI, dinvA, dlog, dsq, dXj, dy, dsvz, dz, dfY, dfYc, dyhat, dsc, dsv1;
+    DBuf<double> dPAI, dinvA, dlog, dsq, dXj, dy, dsvz, dz, dfY, dfYc, dyhat, dsc, dsv1, dfYp, dfYm;
     DBuf<uint8_t> dmask;
     DBuf<int> dst;
     up(dPAI, PAI, (size_t)B * K * N);
@@ -397,11 +484,22 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
     a.seed = seed; a.sweep = (uint32_t)sweep;
     a.fY = dfY.p; a.fYc = dfYc.p; a.yhat = dyhat.p; a.scores = dsc.p; a.status = dst.p;
     a.gl = gl_nodes();
+    if (irf) {
+      dfYp.alloc(nout);
+      dfYm.alloc(nout);
+      a.irfScale = irf1scale;
+      a.fY1p = dfYp.p;
+      a.fY1m = dfYm.p;
+    }
     dsv1.alloc((size_t)B * Nd * N);
     HIPCHECK(launch_fcst(ctx->stream, a, dsv1.p, ctx->opt[OPT_FCST_REG] != 0));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(fcstY, dfY.p, nout * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(fcstYcensor, dfYc.p, nout * sizeof(double), hipMemcpyDeviceToHost));
+    if (irf) {
+      HIPCHECK(hipMemcpy(fcstY1plus, dfYp.p, nout * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHECK(hipMemcpy(fcstY1minus, dfYm.p, nout * sizeof(double), hipMemcpyDeviceToHost));
+    }
     HIPCHECK(hipMemcpy(yhat, dyhat.p, (size_t)B * N * H * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(scores, dsc.p, (size_t)B * 4 * Nd * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<int> st(B);
@@ -414,6 +512,24 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
     if (rc) set_last_error("censored log score with >= 3 series at the ELB (mvncdf) is NaN");
     return rc;
   });
+}
+
+int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI,
+              const double* invA, const double* logSV0, const double* sqrtPHI,
+              const double* Xjumpoff, const double* yrealized, const uint8_t* ndxYields,
+              double elb, const double* svz, const double* z, uint64_t seed, int sweep,
+              double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status) {
+  return fcst_dropin(ctx, B, N, p, H, Nd, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, elb, svz, z, seed,
+                     sweep, fcstY, fcstYcensor, yhat, scores, status, false, 0.0, nullptr, nullptr);
+}
+
+int ccmm_fcst_irf1(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI, const double* invA,
+                   const double* logSV0, const double* sqrtPHI, const double* Xjumpoff, const double* yrealized,
+                   const uint8_t* ndxYields, double elb, const double* svz, const double* z, uint64_t seed, int sweep,
+                   double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status, double irf1scale,
+                   double* fcstY1plus, double* fcstY1minus) {
+  return fcst_dropin(ctx, B, N, p, H, Nd, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, elb, svz, z, seed,
+                     sweep, fcstY, fcstYcensor, yhat, scores, status, true, irf1scale, fcstY1plus, fcstY1minus);
 }
 
 }  // extern "C"

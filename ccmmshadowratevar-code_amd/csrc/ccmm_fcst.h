@@ -57,6 +57,12 @@ struct FcstArgs {
   int mode;               // kFcst* bits below; 0 in production
   int hc;                 // horizons per shock chunk of k_fcst (fcst_paths_lds_doubles)
   double* sv1;            // [B][Nd][N] SV at horizon 1 of each draw (k_fcst -> k_fcst_scores)
+  // doIRF1 (mcmcVARshadowrateBlockHybrid.m:627-664, mcmcVARhybridGibbs.m:638-675, mcmcVARshadowrate.m:588-605):
+  // on when fY1p is set.  The draw's simulation run twice more on the same shocks, with the first variable's
+  // structural shock at horizon 1 replaced by +irfScale / -irfScale (the value itself, not times the volatility)
+  double irfScale;
+  double* fY1p;           // [B][Nd][H][N]  raw plus paths (bh: the shadow recursion, unfloored; linear: ltitr)
+  double* fY1m;           // [B][Nd][H][N]  raw minus paths
 };
 
 // bits of FcstArgs::mode: none selects what is computed; both are timing-only (CCMM_FCST_MODE, ablation build;
@@ -89,6 +95,25 @@ inline int fcst_chunk(int N, int Kx, int p, int H, bool reg = false) {
   return hc;
 }
 
+// The IRF form k_fcst<RN, true> runs the plus and the minus recursion beside the baseline in the same wave; each
+// has a ring pair of its own after the shock chunks (the linear model's plus / minus runs are the unfloored
+// recursion only: one ring each):
+//   [PAI Kx N (LDS form)] sqrtPHI N N | invA N N | ringl p N | ringc p N | W hc N | NU hc N | DV hc N |
+//   bh = 0:  ringl+ p N | ringl- p N
+//   bh > 0:  ringl+ p N | ringc+ p N | ringl- p N | ringc- p N
+__host__ __device__ inline size_t fcst_irf_rings(int bh) { return bh ? 4 : 2; }
+
+__host__ __device__ inline size_t fcst_irf_lds_doubles(int N, int Kx, int p, int hc, bool reg, int bh) {
+  return fcst_paths_lds_doubles(N, Kx, p, hc, reg) + fcst_irf_rings(bh) * (size_t)p * N;
+}
+
+// fcst_chunk for the IRF form
+inline int fcst_irf_chunk(int N, int Kx, int p, int H, bool reg, int bh) {
+  int hc = reg ? std::min(H, 16) : H;
+  while (hc > 1 && fcst_irf_lds_doubles(N, Kx, p, hc, reg, bh) * sizeof(double) > kLdsCu) hc = (hc + 1) / 2;
+  return hc;
+}
+
 // the k_fcst<RN> instance launch_fcst takes: kFcstRegN - 1 (even N below kFcstRegN), kFcstRegN (the other
 // register-path shapes) or 0 (PAI in LDS).  reg_opt: option fcst_reg
 inline int fcst_variant(int N, int p, int bh, bool reg_opt) {
@@ -97,7 +122,8 @@ inline int fcst_variant(int N, int p, int bh, bool reg_opt) {
 }
 
 // k_fcst<RN> then k_fcst_scores of one kept draw per chain; sets a.hc and a.sv1.  reg_opt: option fcst_reg.
-// Throws std::runtime_error when the paths' state does not fit one CU's LDS
+// With a.fY1p set the IRF form k_fcst<RN, true> on the plan of fcst_irf_chunk / fcst_irf_lds_doubles; else the
+// kernels, grid, LDS size and hc of the plain form.  Throws std::runtime_error when the paths' state does not fit one CU's LDS
 hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt);
 // Xjumpoff of every chain from its Y slab (and, block hybrid / hybrid with Ns > 0, the slot's actual data); one
 // workgroup per chain
@@ -108,5 +134,11 @@ hipError_t launch_fcst_jumpoff(hipStream_t st, const FcstArgs& a, int TP, const 
 // store at index m
 hipError_t launch_fcst_accum(hipStream_t st, const FcstArgs& a, int cap, int m, const double* yhat, double* sum,
                              double* sumc, double* sumhat, double* scStore, double* paths, double* pathsc);
+// the kept draw's IRF1 records from a.fY, a.fY1p, a.fY1m (after launch_fcst): recP / recM [B][cap][H][N] at index
+// m, the running sums sumP / sumM [B][H][N], and (when given) the raw paths into pathsP / pathsM at index m.
+// cumcode: [N] rows cumulated over the horizons; tmp: [B][2][H][N] scratch
+hipError_t launch_fcst_irf_accum(hipStream_t st, const FcstArgs& a, int cap, int m, const uint8_t* cumcode,
+                                 double* recP, double* recM, double* sumP, double* sumM, double* tmp, double* pathsP,
+                                 double* pathsM);
 
 }  // namespace ccmm

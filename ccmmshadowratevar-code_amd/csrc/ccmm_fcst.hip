@@ -359,7 +359,14 @@ __device__ double score_censored(const double* invA, const double* sv, const dou
 // a.sv1 for k_fcst_scores.
 //
 
-template <int RN>
+// IRF (doIRF1: BlockHybrid.m:627-664, mcmcVARhybridGibbs.m:638-675, mcmcVARshadowrate.m:588-605): the draw's
+// simulation twice more on the same shocks, w(1,1) = +a.irfScale and -a.irfScale; only horizon 1's nu = invA w
+// differs.  The three recursions (r = 0 baseline, 1 plus, 2 minus) run interleaved in the wave, horizon by horizon,
+// on the same coefficients, Xj, NUb and syncs, each on a ring pair and accumulators of its own (layout:
+// ccmm_fcst.h fcst_irf_lds_doubles).  Block hybrid / hybrid: the baseline's recursion with max(shadow, ELB) in the
+// actual-rate ring; linear: the unfloored recursion only (ltitr, mcmcVARshadowrate.m:596, 602).  The baseline's
+// operations and their order are those of the plain form.
+template <int RN, bool IRF = false>
 __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
   extern __shared__ double sm[];
   const int job = blockIdx.x, c = blockIdx.y;
@@ -369,6 +376,7 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
   if (job >= njobs) return;
   const bool mean_path = job == Nd;
   constexpr bool REG = RN > 0;
+  constexpr int NR = IRF ? 3 : 1;  // recursions of the job
   double* sPAI = sm;                          // Kx x N (column i = equation i); none when REG
   double* sSq = sPAI + (REG ? 0 : (size_t)Kx * N);  // sqrtPHI, N x N column-major
   double* sinvA = sSq + N * N;                // invA, N x N column-major
@@ -405,6 +413,17 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
   rng.chain = a.ids ? a.ids[c] : (uint32_t)c;
   rng.sweep = a.sweep;
   const int nsv = N * H * Nd;
+  // IRF: the plus and minus rings, p x N each (linear: ringl only, rC[r] is not read)
+  double* rL[NR];
+  double* rC[NR];
+  rL[0] = ringl;
+  rC[0] = ringc;
+  const bool dual = !IRF || a.bh != 0;  // recursions 1, 2 carry an actual-rate ring
+#pragma unroll
+  for (int r = 1; r < NR; ++r) {
+    rL[r] = DVb + (size_t)hc * N + (size_t)(r - 1) * (a.bh ? 2 : 1) * p * N;
+    rC[r] = a.bh ? rL[r] + p * N : rL[r];
+  }
   // ring blocks: slot (head - l) mod p holds lag l+1 (l = 0..p-1)
   for (int e = lane; e < p * N; e += 64) {
     const int l = e / N, j = e - l * N;  // lag l+1 goes to slot (-l) mod p
@@ -418,7 +437,15 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
       for (int q = 0; q < a.Ns && q < kElbNsMax; ++q)
         if (hs[q] == j) cv = Xj[K + l * a.Ns + q];
     ringc[slot * N + j] = cv;
+#pragma unroll
+    for (int r = 1; r < NR; ++r) {  // the same jump-off (fcstX0 = Xjumpoff, :632, 648)
+      if (a.bh) rC[r][slot * N + j] = cv;
+      rL[r][slot * N + j] = Xj[1 + e];
+    }
   }
+  double nu1[NR];  // IRF: nu(lane) of horizon 1 in the plus / minus run (lanes < N)
+#pragma unroll
+  for (int r = 0; r < NR; ++r) nu1[r] = 0.0;
   double logsv = (lane < N) ? a.logSV[((size_t)c * N + lane) * a.ldSV + tsv] : 0.0;
   const int G = N <= 21 ? 3 : (N <= 32 ? 2 : 1);  // lane groups of the lag sums (G N <= 64)
   const int g = lane / N, gi = lane - g * N;
@@ -476,84 +503,139 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
         NUb[q] = nu;
       }
       wave_lds_sync();
+      if (IRF && h0 == 0 && lane < N) {  // horizon 1: nushocks(1,1,nn) = +-IRF1scale, then invA_ * nushocks (:630-631, 646-647)
+#pragma unroll
+        for (int r = 1; r < NR; ++r) {
+          const double w0 = r == 1 ? a.irfScale : -a.irfScale;
+          double nu = 0.0;
+          for (int j = 0; j <= lane; ++j) nu = fma(sinvA[lane + j * N], j == 0 ? w0 : Wb[j], nu);
+          nu1[r] = nu;
+        }
+      }
     }
     for (int hq = 0; hq < nh; ++hq) {
       const int hh = h0 + hq;
       // fcstA * state on the lane groups
-      double sl2 = 0.0, sc = 0.0;
+      double sl2[NR], sc[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) sl2[r] = sc[r] = 0.0;
       if (REG) {
         if (g < G) {
-          if (g == 0) sl2 = sc = Xj[0] * c0;
+          if (g == 0) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) sl2[r] = sc[r] = Xj[0] * c0;
+          }
 #pragma unroll
           for (int m = 0; m < (REG ? kFcstRegLags : 1); ++m) {
             const int l = g + G * m;
             if (l < p) {
               int slot = head - l;
               slot += (slot < 0) ? p : 0;
-              const double* rl = ringl + slot * N;
-              const double* rc = ringc + slot * N;
+              const double* rl[NR];
+              const double* rc[NR];
+#pragma unroll
+              for (int r = 0; r < NR; ++r) {
+                rl[r] = rL[r] + slot * N;
+                rc[r] = rC[r] + slot * N;
+              }
               if (RN % 2 == 0) {  // N even: the ring rows are 16-byte aligned, two lags' entries a read
 #pragma unroll
                 for (int j = 0; j < (REG ? RN : 1); j += 2)
                   if (j < N) {
-                    const double2 vl = *reinterpret_cast<const double2*>(rl + j);
-                    const double2 vc = *reinterpret_cast<const double2*>(rc + j);
-                    sl2 = fma(cf[m][j], vl.x, sl2);
-                    sc = fma(cf[m][j], vc.x, sc);
-                    sl2 = fma(cf[m][j + 1], vl.y, sl2);
-                    sc = fma(cf[m][j + 1], vc.y, sc);
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) {
+                      const double2 vl = *reinterpret_cast<const double2*>(rl[r] + j);
+                      if (r == 0 || dual) {
+                        const double2 vc = *reinterpret_cast<const double2*>(rc[r] + j);
+                        sl2[r] = fma(cf[m][j], vl.x, sl2[r]);
+                        sc[r] = fma(cf[m][j], vc.x, sc[r]);
+                        sl2[r] = fma(cf[m][j + 1], vl.y, sl2[r]);
+                        sc[r] = fma(cf[m][j + 1], vc.y, sc[r]);
+                      } else {
+                        sl2[r] = fma(cf[m][j], vl.x, sl2[r]);
+                        sl2[r] = fma(cf[m][j + 1], vl.y, sl2[r]);
+                      }
+                    }
                   }
               } else {
 #pragma unroll
                 for (int j = 0; j < (REG ? RN : 1); ++j)
                   if (j < N) {
-                    sl2 = fma(cf[m][j], rl[j], sl2);
-                    sc = fma(cf[m][j], rc[j], sc);
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) {
+                      sl2[r] = fma(cf[m][j], rl[r][j], sl2[r]);
+                      if (r == 0 || dual) sc[r] = fma(cf[m][j], rc[r][j], sc[r]);
+                    }
                   }
               }
             }
           }
         }
       } else if (g < G) {
-        if (g == 0) sl2 = sc = Xj[0] * pcol[0];  // constant state stays 1 (fcstA(1,1) = 1)
+        if (g == 0) {  // constant state stays 1 (fcstA(1,1) = 1)
+#pragma unroll
+          for (int r = 0; r < NR; ++r) sl2[r] = sc[r] = Xj[0] * pcol[0];
+        }
         for (int l = g; l < p; l += G) {
           int slot = head - l;
           slot += (slot < 0) ? p : 0;
-          const double* rl = ringl + slot * N;
-          const double* rc = ringc + slot * N;
+          const double* rl[NR];
+          const double* rc[NR];
+#pragma unroll
+          for (int r = 0; r < NR; ++r) {
+            rl[r] = rL[r] + slot * N;
+            rc[r] = rC[r] + slot * N;
+          }
           const double* pc = pcol + 1 + l * N;
 #pragma unroll 4
           for (int j = 0; j < N; ++j) {
-            sl2 = fma(pc[j], rl[j], sl2);
-            sc = fma(pc[j], rc[j], sc);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+              sl2[r] = fma(pc[j], rl[r][j], sl2[r]);
+              if (r == 0 || dual) sc[r] = fma(pc[j], rc[r][j], sc[r]);
+            }
           }
           if (hy)  // fcstA(ndxfcstY, Kshadow+1:end) on the actual-rate ring (:626)
-            for (int q = 0; q < a.Ns && q < kElbNsMax; ++q) sl2 = fma(pcol[K + l * a.Ns + q], rc[hs[q]], sl2);
+            for (int q = 0; q < a.Ns && q < kElbNsMax; ++q) {
+#pragma unroll
+              for (int r = 0; r < NR; ++r) sl2[r] = fma(pcol[K + l * a.Ns + q], rc[r][hs[q]], sl2[r]);
+            }
         }
       }
       // every group's partial is read before any lane adds (lane i + N is also the source of
       // lane i's group-2 partial through lane i + 2N ... and must still hold its own)
-      double pl[2] = {0.0, 0.0}, pcs[2] = {0.0, 0.0};
+      double pl[NR][2], pcs[NR][2];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) pl[r][0] = pl[r][1] = pcs[r][0] = pcs[r][1] = 0.0;
       for (int q = 1; q < G; ++q) {
-        pl[q - 1] = __shfl(sl2, lane + q * N, 64);
-        pcs[q - 1] = __shfl(sc, lane + q * N, 64);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          pl[r][q - 1] = __shfl(sl2[r], lane + q * N, 64);
+          if (r == 0 || dual) pcs[r][q - 1] = __shfl(sc[r], lane + q * N, 64);
+        }
       }
       for (int q = 1; q < G; ++q) {
-        sl2 += pl[q - 1];
-        sc += pcs[q - 1];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          sl2[r] += pl[r][q - 1];
+          sc[r] += pcs[r][q - 1];
+        }
       }
       double yl = 0.0, yc = 0.0;
+      double yx[NR], ycx[NR];  // IRF: the plus / minus values (entries 1, 2)
+#pragma unroll
+      for (int r = 0; r < NR; ++r) yx[r] = ycx[r] = 0.0;
       if (lane < N) {
         const double nu = mean_path ? 0.0 : NUb[hq * N + lane];
         if (hy) {
-          yl = sl2 + nu;
+          yl = sl2[0] + nu;
           yc = (isyield && yl < a.elb) ? a.elb : yl;  // yields floored (:707-711); ring: max(shadow, ELB) (:634)
         } else if (a.bh) {
-          yl = (isact ? sc : sl2) + nu;               // fcstA * fcstX0 + fcstB * shocks (:615)
+          yl = (isact ? sc[0] : sl2[0]) + nu;         // fcstA * fcstX0 + fcstB * shocks (:615)
           yc = (isyield && yl < a.elb) ? a.elb : yl;  // actual rate max(shadow, ELB) (:623)
         } else {
-          yl = sl2 + nu;
-          yc = sc + nu;
+          yl = sl2[0] + nu;
+          yc = sc[0] + nu;
           if (isrec && yc < a.elb) yc = a.elb;        // censored simulation (mcmcVAR.m:360-366)
         }
         if (mean_path) {
@@ -562,6 +644,16 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
           const size_t o = (((size_t)c * Nd + job) * H + hh) * N + lane;
           a.fY[o] = yl;
           a.fYc[o] = yc;
+          if (IRF) {  // fcstYdraws1plus / fcstYdraws1minus as simulated (:639, 657); linear: no floor inside
+#pragma unroll
+            for (int r = 1; r < NR; ++r) {
+              const double nux = hh == 0 ? nu1[r] : nu;
+              yx[r] = (isact ? sc[r] : sl2[r]) + nux;  // (isact: block hybrid only)
+              ycx[r] = (isyield && yx[r] < a.elb) ? a.elb : yx[r];
+            }
+            a.fY1p[o] = yx[IRF ? 1 : 0];
+            a.fY1m[o] = yx[IRF ? 2 : 0];
+          }
         }
       }
       wave_lds_sync();  // every lane has read the oldest lag block before it is overwritten
@@ -569,6 +661,11 @@ __global__ __launch_bounds__(64, 2) void k_fcst(FcstArgs a) {
       if (lane < N) {
         ringl[head * N + lane] = yl;
         ringc[head * N + lane] = yc;
+#pragma unroll
+        for (int r = 1; r < NR; ++r) {
+          rL[r][head * N + lane] = yx[r];
+          if (dual) rC[r][head * N + lane] = ycx[r];
+        }
       }
       wave_lds_sync();
     }
@@ -757,21 +854,97 @@ __global__ void k_fcst_accum(int N, int H, int Nd, int cap, int m, const double*
     }
 }
 
+// Per kept draw, the IRF1 records (BlockHybrid.m:702-737, mcmcVARhybridGibbs.m:713-748, mcmcVARshadowrate.m:
+// 649-684), one workgroup per chain: the yields of the plus, minus and baseline paths floored at the ELB, irfdraws =
+// floored plus (minus) - floored baseline, its mean over the Nd draws (summed in draw order) into recP / recM at
+// index m, the sum over the draws of the floored plus (minus) paths into sumP / sumM; the rows of cumcode run as
+// cumulative sums over the horizons (cumsum(., 2)) in all four.  Three passes: the sums over the draws of every
+// entry (h, i) (into the record and tmp, [B][2][H][N]); the running sums of the cumulated rows, one thread per
+// (row, array) with eight horizons' loads in flight; the division and the update of the running sums.  Optionally
+// the raw paths into the store.
+__global__ void k_fcst_irf_accum(int N, int H, int Nd, int cap, int m, double elb, const uint8_t* __restrict__ yields,
+                                 const uint8_t* __restrict__ cum, const double* __restrict__ fY,
+                                 const double* __restrict__ fYp, const double* __restrict__ fYm,
+                                 double* __restrict__ recP, double* __restrict__ recM, double* __restrict__ sumP,
+                                 double* __restrict__ sumM, double* __restrict__ tmp, double* __restrict__ pathsP,
+                                 double* __restrict__ pathsM) {
+  const int c = blockIdx.x;
+  const size_t HN = (size_t)H * N, per = (size_t)Nd * HN;
+  const double* y = fY + (size_t)c * per;
+  const double* yp = fYp + (size_t)c * per;
+  const double* ym = fYm + (size_t)c * per;
+  double* arr[4] = {recP + ((size_t)c * cap + m) * HN, recM + ((size_t)c * cap + m) * HN, tmp + (size_t)c * 2 * HN,
+                    tmp + (size_t)c * 2 * HN + HN};
+  for (size_t q = threadIdx.x; q < HN; q += blockDim.x) {
+    const bool fl = yields[q % N] != 0;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int job = 0; job < Nd; ++job) {
+      double b = y[(size_t)job * HN + q], up = yp[(size_t)job * HN + q], um = ym[(size_t)job * HN + q];
+      if (fl) {
+        b = b < elb ? elb : b;
+        up = up < elb ? elb : up;
+        um = um < elb ? elb : um;
+      }
+      v[0] += up - b;
+      v[1] += um - b;
+      v[2] += up;
+      v[3] += um;
+    }
+    for (int k = 0; k < 4; ++k) arr[k][q] = v[k];
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < 4 * N; t += blockDim.x) {
+    const int k = t / N, i = t - k * N;
+    if (!cum[i]) continue;
+    double* x = arr[k] + i;
+    double run = 0.0;
+    for (int h0 = 0; h0 < H; h0 += 8) {
+      double v[8];
+      for (int u = 0; u < 8; ++u) v[u] = h0 + u < H ? x[(size_t)(h0 + u) * N] : 0.0;
+      for (int u = 0; u < 8; ++u)
+        if (h0 + u < H) {
+          run += v[u];
+          x[(size_t)(h0 + u) * N] = run;
+        }
+    }
+  }
+  __syncthreads();
+  for (size_t q = threadIdx.x; q < HN; q += blockDim.x) {
+    arr[0][q] /= Nd;
+    arr[1][q] /= Nd;
+    sumP[(size_t)c * HN + q] += arr[2][q];
+    sumM[(size_t)c * HN + q] += arr[3][q];
+  }
+  if (pathsP)
+    for (size_t q = threadIdx.x; q < per; q += blockDim.x) {
+      pathsP[((size_t)c * cap + m) * per + q] = yp[q];
+      pathsM[((size_t)c * cap + m) * per + q] = ym[q];
+    }
+}
+
 
 // ------------------------------------------------------------------ host launchers
 // the paths (one single-wave workgroup per (draw, chain); job Nd = the linear model's mean path) then the scores
 hipError_t launch_fcst(hipStream_t st, FcstArgs& a, double* sv1, bool reg_opt) {
   const bool reg = fcst_reg_path(a.N, a.p, a.bh) && reg_opt;
-  a.hc = fcst_chunk(a.N, a.Kx, a.p, a.H, reg);
+  const bool irf = a.fY1p != nullptr;
+  a.hc = irf ? fcst_irf_chunk(a.N, a.Kx, a.p, a.H, reg, a.bh) : fcst_chunk(a.N, a.Kx, a.p, a.H, reg);
   a.sv1 = sv1;
-  const size_t lp = fcst_paths_lds_doubles(a.N, a.Kx, a.p, a.hc, reg) * sizeof(double);
+  const size_t lp = (irf ? fcst_irf_lds_doubles(a.N, a.Kx, a.p, a.hc, reg, a.bh)
+                         : fcst_paths_lds_doubles(a.N, a.Kx, a.p, a.hc, reg)) * sizeof(double);
   const size_t ls = fcst_scores_lds_doubles(a.N) * sizeof(double);
   if (lp > kLdsCu) throw std::runtime_error("forecast state does not fit LDS");
   const dim3 g(a.bh ? a.Nd : a.Nd + 1, a.B);
   const int rn = fcst_variant(a.N, a.p, a.bh, reg_opt);
-  const hipError_t e = rn == kFcstRegN - 1 ? launch_k(k_fcst<kFcstRegN - 1>, g, dim3(64), lp, true, st, a)
-                       : rn == kFcstRegN   ? launch_k(k_fcst<kFcstRegN>, g, dim3(64), lp, true, st, a)
-                                           : launch_k(k_fcst<0>, g, dim3(64), lp, true, st, a);
+  hipError_t e;
+  if (irf)
+    e = rn == kFcstRegN - 1 ? launch_k(k_fcst<kFcstRegN - 1, true>, g, dim3(64), lp, true, st, a)
+        : rn == kFcstRegN   ? launch_k(k_fcst<kFcstRegN, true>, g, dim3(64), lp, true, st, a)
+                            : launch_k(k_fcst<0, true>, g, dim3(64), lp, true, st, a);
+  else
+    e = rn == kFcstRegN - 1 ? launch_k(k_fcst<kFcstRegN - 1>, g, dim3(64), lp, true, st, a)
+        : rn == kFcstRegN   ? launch_k(k_fcst<kFcstRegN>, g, dim3(64), lp, true, st, a)
+                            : launch_k(k_fcst<0>, g, dim3(64), lp, true, st, a);
   if (e != hipSuccess) return e;
   return launch_k(k_fcst_scores, dim3(a.Nd, a.B), dim3(64), ls, true, st, a);
 }
@@ -786,6 +959,14 @@ hipError_t launch_fcst_accum(hipStream_t st, const FcstArgs& a, int cap, int m, 
                              double* sumc, double* sumhat, double* scStore, double* paths, double* pathsc) {
   return launch_k(k_fcst_accum, dim3(a.B), dim3(256), 0, false, st, a.N, a.H, a.Nd, cap, m, a.fY, a.fYc, yhat, a.scores, sum, sumc,
                   sumhat, scStore, paths, pathsc);
+}
+
+hipError_t launch_fcst_irf_accum(hipStream_t st, const FcstArgs& a, int cap, int m, const uint8_t* cumcode,
+                                 double* recP, double* recM, double* sumP, double* sumM, double* tmp, double* pathsP,
+                                 double* pathsM) {
+  return launch_k(k_fcst_irf_accum, dim3(a.B), dim3(256), 0, false, st, a.N, a.H, a.Nd, cap, m, a.elb, a.ndxYields, cumcode,
+                  (const double*)a.fY, (const double*)a.fY1p, (const double*)a.fY1m, recP, recM, sumP, sumM, tmp, pathsP,
+                  pathsM);
 }
 
 }  // namespace ccmm

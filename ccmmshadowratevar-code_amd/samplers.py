@@ -5,7 +5,7 @@
 ``nchains``: B independent chains run as one device batch (the
 ``goVAR*`` parfor over vintages/chains becomes one GPU launch sequence).
 ``mcmcVARshadowrateBlockHybrid`` mirrors the block-hybrid shadow-rate sampler
-(outputs 1-13: draws and the predictive density).  ``goVARshadowrateBlockHybrid_batch``
+(outputs 1-13: draws and the predictive density; 14-19 with IRF1scale: the in-sampler impulse responses).  ``goVARshadowrateBlockHybrid_batch``
 is the quasi-real-time OOS run over all vintages as one device batch per GPU.  ``CTA``/``CTAsys``/``CTAsysAswitching``/``drawTruncNormal`` mirror the L2 functions.
 
 Every numerical step goes through ``libccmm.so``; there is no CPU fallback.
@@ -265,12 +265,13 @@ _MODELS = {
 
 def _run_single(model, bm, nchains, MCMCdraws, *, ndxYIELDS, ELBbound, yrealized, fcstNdraws, fcstNhorizons,
                 rndStream, doprogress, device, burnin, gibbsburn, Nproposals, elb_ps=True, missing=False,
-                alternate=False, check_stationarity=0, stats=None, want_ps=True):
+                alternate=False, check_stationarity=0, stats=None, want_ps=True, IRF1scale=None, IRFcumcode=None):
     """One vintage ``bm`` as the one-unit chain set of _bh_chain_set with C = nchains, run for the three
     single-vintage samplers.  Returns a namespace of the raw products, each with the trailing chain axis:
     draws (PAI_all, PHI_all, invA_all, sqrtht_all, shadowrate_all, missingrate_all; missingrate_all NaN where
     the sweep kept none), fc (Chains.get_fcst with the paths, or None), ps (Chains.get_ps, or None when no
-    sweep proposed or ``want_ps`` is false) and yields (bool N).  ``stats`` receives stationarityRedraws."""
+    sweep proposed or ``want_ps`` is false), yields (bool N) and irf (Chains.get_irf1, or None without
+    IRF1scale).  ``stats`` receives stationarityRedraws."""
     spec, m, B = _MODELS[model], bm.var, int(nchains)
     burn = MCMCdraws if burnin is None else int(burnin)
     dens = bool(fcstNdraws)
@@ -280,12 +281,15 @@ def _run_single(model, bm, nchains, MCMCdraws, *, ndxYIELDS, ELBbound, yrealized
                                   gibbsburn=gibbsburn, ELBbound=ELBbound, ndxYIELDS=ndxYIELDS,
                                   fcstNhorizons=int(fcstNhorizons) if dens else None,
                                   Nd=fcstNdraws // MCMCdraws if dens else None, keep_paths=True, model=model)
+    if IRF1scale is not None:
+        ch.set_irf1(IRF1scale, IRFcumcode)
     use_ps = _bh_switches(ch, spec, burn, Nproposals=Nproposals, elb_ps=elb_ps, missing=missing,
                           alternate=alternate, keep_missingrate=spec.ps_missingrate,
                           check_stationarity=check_stationarity)
     _run_chain_set(ch, burn, MCMCdraws, doprogress)
     _stationarity_stats(ch, check_stationarity, stats)
     ps = ch.get_ps() if use_ps and want_ps else None
+    irf = ch.get_irf1() if IRF1scale is not None else None  # (before get_fcst, which resets the records)
     fc = ch.get_fcst(paths=True) if dens else None
     kept = missing or alternate or (use_ps and spec.ps_missingrate)
     miss = ch.get_missingrate() if kept and bm.elbT else np.full((MCMCdraws, len(bm.ndxS), bm.elbT, B), np.nan)
@@ -293,7 +297,21 @@ def _run_single(model, bm, nchains, MCMCdraws, *, ndxYIELDS, ELBbound, yrealized
     ch.close()
     draws = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"],
              out["shadowrate_all"][:, :, :bm.elbT], miss[:, :, :bm.elbT]]
-    return SimpleNamespace(draws=draws, fc=fc, ps=ps, yields=yields)
+    return SimpleNamespace(draws=draws, fc=fc, ps=ps, yields=yields, irf=irf)
+
+
+def _check_irf1(IRF1scale, doPredictiveDensity):
+    """IRF1scale is not None plays the role of doIRF1 (nargout > 13; > 17 in mcmcVARshadowrate): the plus and
+    minus simulations belong to the predictive density's loop over the forecast draws."""
+    if IRF1scale is not None and not doPredictiveDensity:
+        raise ValueError("IRF1scale needs the predictive density (fcstNdraws)")
+
+
+def _irf1_outputs(irf, fcstNdraws):
+    """IRF1plus, IRF1minus (N x H), IRF1drawsPlus, IRF1drawsMinus (N x H x MCMCdraws), fcstY1hatPlus,
+    fcstY1hatMinus (N x H) of a get_irf1 record, each with the trailing chain axis (BlockHybrid.m:702-737)."""
+    dP, dM = irf["drawsPlus"], irf["drawsMinus"]
+    return [dP.mean(axis=2), dM.mean(axis=2), dP, dM, irf["y1sumPlus"] / fcstNdraws, irf["y1sumMinus"] / fcstNdraws]
 
 
 def _check_fcst_draws(fcstNdraws, MCMCdraws, *needed):
@@ -335,12 +353,17 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
     receives countELBaccept / countELBacceptBurnin / stackAccept (:303-305, 453-460).
     check_stationarity=1 (:333-347): PAI is drawn again while its companion's maximum root is >= 1;
     ``stats`` then also receives stationarityRedraws (per chain).
+    IRF1scale (not None: doIRF1, the reference's nargout > 13; needs fcstNdraws) and IRFcumcode (0-based indices
+    or a bool vector of the rows cumulated over the horizons) append outputs 14-19 (:627-664, 702-737):
+    IRF1plus, IRF1minus (N x H), IRF1drawsPlus, IRF1drawsMinus (N x H x MCMCdraws), fcstY1hatPlus,
+    fcstY1hatMinus (N x H) -- every kept draw's predictive simulation run twice more on the same shocks with the
+    structural shock of variable 1 at horizon 1 replaced by +IRF1scale / -IRF1scale, on the device
+    (Chains.set_irf1); the other outputs are those of the call without them.
     Indices are 0-based; actualrateBlock is a bool vector of length N."""
     if not doELBsampling and not doELBsampleAlternate:
         _refuse_gibbs_on_nan("mcmcVARshadowrateBlockHybrid.m:494")
-    if IRF1scale is not None:
-        raise NotImplementedError("IRF outputs (doIRF1): use samplers.generateGIRF")
     doPredictiveDensity = _check_fcst_draws(fcstNdraws, MCMCdraws, yrealized, fcstNhorizons)  # :123-126
+    _check_irf1(IRF1scale, doPredictiveDensity)
     bm = _MODELS["blockhybrid"].build(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
                                       minnesotaPriorMean, ELBbound, elbT0, doRATSprior, actualrateBlock)
     if bm.warn_elbT0:
@@ -351,7 +374,8 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
                     rndStream=rndStream, doprogress=doprogress, device=device, burnin=burnin,
                     gibbsburn=gibbsburn, Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling,
                     alternate=bool(doELBsampling and doELBsampleAlternate),
-                    check_stationarity=check_stationarity, stats=stats, want_ps=stats is not None)
+                    check_stationarity=check_stationarity, stats=stats, want_ps=stats is not None,
+                    IRF1scale=IRF1scale, IRFcumcode=IRFcumcode)
     if r.ps is not None:
         stats.update(countELBaccept=r.ps["countAccept"], countELBacceptBurnin=r.ps["countAcceptBurnin"],
                      stackAccept=r.ps["stackAccept"])
@@ -363,6 +387,8 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
         fYd = r.fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F")
         fSd = r.fc["paths"][r.yields].reshape(int(r.yields.sum()), H, fcstNdraws, B, order="F")
         res += [fYd, fYd.mean(axis=2), fSd, fSd.mean(axis=2)] + _score_draws(r.fc, fcstNdraws, B)
+        if r.irf is not None:  # outputs 14-19 (:702-737)
+            res += _irf1_outputs(r.irf, fcstNdraws)
     return _drop_chain_axis(res, int(nchains))
 
 
@@ -382,12 +408,14 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
     shadowrate_all is NaN), fcstYdraws, fcstYhat, fcstYcensorDraws, fcstYcensorHat, fcstShadowrateDraws, fcstShadowrateHat,
     fcstYhatRB, fcstLogscoreDraws, fcstLogscoreXdraws, fcstLogscoreIdraws, stackAccept
     (:630-700).  check_stationarity=1: PAI is drawn again while its companion's maximum root is >= 1;
-    ``stats`` then also receives stationarityRedraws (per chain).  Indices 0-based."""
+    ``stats`` then also receives stationarityRedraws (per chain).  IRF1scale (not None: the reference's
+    nargout > 17; needs fcstNdraws) and IRFcumcode append outputs 18-23 after stackAccept (:588-605, 649-684):
+    IRF1plus, IRF1minus, IRF1drawsPlus, IRF1drawsMinus, fcstY1hatPlus, fcstY1hatMinus, the plus / minus runs on
+    the linear recursion (ltitr) against fcstYdraws with its yields floored afterwards.  Indices 0-based."""
     if doPAIactual:
         raise NotImplementedError("doPAIactual = true (CTA on the actual data, :322-324) is not built")
-    if IRF1scale is not None:
-        raise NotImplementedError("in-sampler IRF outputs: use samplers.generateGIRF")
     doPredictiveDensity = _check_fcst_draws(fcstNdraws, MCMCdraws)
+    _check_irf1(IRF1scale, doPredictiveDensity)
     bm = _MODELS["shadowrate"].build(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
                                      minnesotaPriorMean, ELBbound, elbT0, doRATSprior)
     ndxY = np.union1d(bm.ndxS, bm.ndxO)
@@ -396,7 +424,7 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
                     yrealized=yrealized, fcstNdraws=fcstNdraws, fcstNhorizons=fcstNhorizons, rndStream=rndStream,
                     doprogress=doprogress, device=device, burnin=burnin, gibbsburn=gibbsburn,
                     Nproposals=Nproposals, missing=not doELBsampling, check_stationarity=check_stationarity,
-                    stats=stats)
+                    stats=stats, IRF1scale=IRF1scale, IRFcumcode=IRFcumcode)
     B = int(nchains)
     stack = np.zeros((MCMCdraws, B), np.int32)
     if r.ps is not None:
@@ -420,6 +448,8 @@ def mcmcVARshadowrate(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMe
         fYhat[ndxY] = fYd[ndxY].mean(axis=2)                  # :683-684
         res += [fYd, fYhat, fYc, fYc.mean(axis=2), fSd, RB[ndxY], RB] + _score_draws(r.fc, fcstNdraws, B)
     res.append(stack)
+    if r.irf is not None:  # outputs 18-23 (:649-684)
+        res += _irf1_outputs(r.irf, fcstNdraws)
     return _drop_chain_axis(res, B)
 
 
@@ -440,14 +470,15 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
     The shadow rates are drawn by accept-first PS proposals at every sweep with the Gibbs
     sampler as fallback (:458-483), the proposal sampler restated from the absent
     em-matlabbox VARTVPSVprecisionsamplerNaN (elb_ps=False: Gibbs every sweep).
-    actualrateWeight is unused, as in the reference (:16).  Indices are 0-based."""
+    actualrateWeight is unused, as in the reference (:16).  IRF1scale (not None: doIRF1, nargout > 13; needs
+    fcstNdraws) and IRFcumcode append outputs 14-19 (:638-675, 713-748) as in mcmcVARshadowrateBlockHybrid.
+    Indices are 0-based."""
     if check_stationarity:
         warnings.warn("no stationarity check for hybrid model")  # :22-24
     if not doELBsampling and not doELBsampleAlternate:
         _refuse_gibbs_on_nan("mcmcVARhybridGibbs.m:513")
-    if IRF1scale is not None:
-        raise NotImplementedError("in-sampler IRF outputs: use samplers.generateGIRF(hybrid=True)")
     doPredictiveDensity = _check_fcst_draws(fcstNdraws, MCMCdraws, yrealized, fcstNhorizons)
+    _check_irf1(IRF1scale, doPredictiveDensity)
     hm = _MODELS["hybrid"].build(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
                                  minnesotaPriorMean, ELBbound, elbT0, doRATSprior)
     if hm.warn_elbT0:
@@ -458,7 +489,8 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
     r = _run_single("hybrid", hm, nchains, MCMCdraws, ndxYIELDS=ndxYIELDS, ELBbound=ELBbound,
                     yrealized=yrealized, fcstNdraws=fcstNdraws, fcstNhorizons=fcstNhorizons, rndStream=rndStream,
                     doprogress=doprogress, device=device, burnin=burnin, gibbsburn=gibbsburn,
-                    Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling, want_ps=stats is not None)
+                    Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling, want_ps=stats is not None,
+                    IRF1scale=IRF1scale, IRFcumcode=IRFcumcode)
     if r.ps is not None:
         stats.update(countELBaccept=r.ps["countAccept"] + r.ps["countAcceptBurnin"],
                      stackAccept=r.ps["stackAccept"])
@@ -469,6 +501,8 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
         fSd = fYu[ndxYIELDS].copy()                                           # fcstShadowrateDraws (:704)
         fYd = r.fc["paths_censored"].reshape(N, H, fcstNdraws, B, order="F")  # yields floored (:707-711)
         res += [fYd, fYd.mean(axis=2), fSd, fSd.mean(axis=2)] + _score_draws(r.fc, fcstNdraws, B)
+        if r.irf is not None:  # outputs 14-19 (:713-748)
+            res += _irf1_outputs(r.irf, fcstNdraws)
     return _drop_chain_axis(res, int(nchains))
 
 

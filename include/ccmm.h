@@ -370,6 +370,30 @@ int ccmm_chains_fcst_stored(const ccmm_chains* ch);
  * CCMM_WARN_MVNCDF when some censored score needed mvncdf in more than 12 dimensions (NaN). */
 int ccmm_chains_get_fcst(ccmm_chains* ch, double* scores, double* fYsum, double* fYcsum,
                          double* yhatsum, double* paths, double* paths_censored);
+/* ---- doIRF1: the impulse responses computed inside the sampler (mcmcVARshadowrateBlockHybrid.m:627-664,
+ *      702-737; mcmcVARhybridGibbs.m:638-675, 713-748; mcmcVARshadowrate.m:588-605, 649-684) ----
+ * Every kept draw's predictive simulation is run twice more on the same shocks, with the structural shock of
+ * variable 1 (index 0) at horizon 1 replaced by +scale and by -scale (the value itself, not times the
+ * volatility); no random number is drawn that the predictive density does not draw.  Block hybrid and hybrid:
+ * the baseline's recursion with the actual rates max(shadow, ELB); mcmcVARshadowrate (and the linear model): the
+ * linear recursion without a floor (ltitr, :596, 602).  Afterwards, per kept draw: the yields (ndxYields) of the
+ * plus, minus and baseline paths floored at the ELB, irfdraws = floored plus (minus) - floored baseline, the rows
+ * of cumcode cumulated over the horizons (cumsum(., 2)), the mean over the Nd draws.
+ *   scale    IRF1scale (finite, else CCMM_ERR_ARG)
+ *   cumcode  N bytes (IRFcumcode as a mask) or NULL (no row cumulated)
+ * Call after ccmm_chains_set_fcst (else CCMM_ERR_STATE; a later set_fcst turns it off again) and before
+ * sweeping; every model.  The predictive density's own records are those of a chain set without it. */
+int ccmm_chains_set_irf1(ccmm_chains* ch, double scale, const uint8_t* cumcode);
+/* Copy out (without resetting) the IRF1 records of the M kept draws so far; ccmm_chains_get_fcst resets them
+ * together with the forecast records, so call this first.
+ *   drawsPlus, drawsMinus    N x H x M x B  IRF1drawsPlus / IRF1drawsMinus (IRF1plus = their mean over M)
+ *   y1sumPlus, y1sumMinus    N x H x B  sum over the M x Nd floored plus / minus paths, cumcode rows cumulated
+ *                            (fcstY1hatPlus / Minus = the sum / (M Nd))
+ *   pathsPlus, pathsMinus    N x H x Nd x M x B  fcstYdraws1plus / minus as simulated (raw: not floored, not
+ *                            cumulated); only with keep_paths
+ * Any pointer may be NULL. */
+int ccmm_chains_get_irf1(ccmm_chains* ch, double* drawsPlus, double* drawsMinus, double* y1sumPlus,
+                         double* y1sumMinus, double* pathsPlus, double* pathsMinus);
 
 /* ---- shadow-rate models: block-hybrid (mcmcVARshadowrateBlockHybrid.m) and
  *      hybrid (mcmcVARhybridGibbs.m) ----
@@ -738,6 +762,15 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
               const double* Xjumpoff, const double* yrealized, const uint8_t* ndxYields,
               double elb, const double* svz, const double* z, uint64_t seed, int sweep,
               double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status);
+/* ccmm_fcst with the doIRF1 simulations of mcmcVARshadowrate.m:588-605: the linear recursion (ltitr) twice more
+ * on the draw's shocks, the structural shock of variable 1 (index 0) at horizon 1 replaced by +irf1scale and by
+ * -irf1scale.  fcstY1plus, fcstY1minus N x H x Nd x B (fcstYdraws1plus / fcstYdraws1minus as simulated, laid out
+ * like fcstY).  Every output of ccmm_fcst is the one ccmm_fcst returns on the same inputs. */
+int ccmm_fcst_irf1(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI, const double* invA,
+                   const double* logSV0, const double* sqrtPHI, const double* Xjumpoff, const double* yrealized,
+                   const uint8_t* ndxYields, double elb, const double* svz, const double* z, uint64_t seed, int sweep,
+                   double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status, double irf1scale,
+                   double* fcstY1plus, double* fcstY1minus);
 
 /* D16x16 = A16x4 * B4x16 computed by one v_mfma_f64_16x16x4_f64 with the operand
  * and accumulator lane maps the CTA SYRK kernel relies on (all column-major). */
