@@ -93,6 +93,7 @@ const ccmm::OptDesc ccmm::kOptDesc[ccmm::kOptCount] = {
     {"phi_overlap", "CCMM_PHI_OVERLAP", 1, 0, 1},
     {"qr_fallback", "CCMM_QR_FALLBACK", 1, 0, 1},
     {"big_lagx", "CCMM_BIG_LAGX", 1, 0, 1},
+    {"phi_stage", "CCMM_PHI_STAGE", 3, 0, 3},
     {"lag", "CCMM_LAG", 1, 0, 1},
     {"large_path", "CCMM_FORCE_BIG", 0, 0, 1},
     {"astep_serial", "CCMM_ASTEP_V1", 0, 0, 1},

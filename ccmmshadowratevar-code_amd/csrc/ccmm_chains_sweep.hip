@@ -202,7 +202,7 @@ void ccmm_chains::run_phi(const RngArgs& ra, hipStream_t on) {
   if (bign)
     launch(KID_PHIBIG, [&] { HIPCHECK(bign_launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs, bigScr.p)); }, st);
   else
-    launch(KID_PHI, [&] { HIPCHECK(launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs)); }, st);
+    launch(KID_PHI, [&] { HIPCHECK(launch_phi(st, d, Tslot.p, cfg.dPHI, sPHI.p, cs, opt[OPT_PHI_STAGE])); }, st);
 }
 
 void ccmm_chains::run_store() {

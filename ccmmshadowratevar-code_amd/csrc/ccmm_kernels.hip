@@ -869,8 +869,9 @@ hipError_t launch_astep(bool serial, hipStream_t st, Dims d, const int* Tslot, C
                   gtab);
 }
 
-hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs) {
-  const PhiPlan pl = phi_plan(d.N, d.TP, dPHI);
+hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs,
+                      int phi_stage) {
+  const PhiPlan pl = phi_plan(d.N, d.TP, dPHI, phi_stage);
   return launch_k(k_phi, dim3(d.B), dim3(256), pl.lds, pl.lds > kLdsDefault, st, d, Tslot, dPHI, sPHIall, cs,
                   pl.stage_eta);
 }

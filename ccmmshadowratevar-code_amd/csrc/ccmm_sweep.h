@@ -117,14 +117,20 @@ struct PhiPlan {
 // bits of stage_eta: what k_phi reads from LDS (the same products in the same order); none is timing-only
 constexpr int kPhiStageEta = 1;  // eta staged with row stride TP + 1
 constexpr int kPhiStageZ = 2;    // Z follows eta into the same region
-inline PhiPlan phi_plan(int N, int TP, int dPHI) {
+// stage_mask (option phi_stage, default 3): the bits the plan may use, for comparing the three forms on one shape.
+// Z is staged into the region eta has been read from, so kPhiStageZ without kPhiStageEta is no form of the kernel:
+// masks 2 and 0 both mean "stage nothing".  The LDS size is that of the masked plan.
+inline PhiPlan phi_plan(int N, int TP, int dPHI, int stage_mask = kPhiStageEta | kPhiStageZ) {
   const size_t lds = (size_t)(4 * N * (N + 1)) * sizeof(double);
   const size_t staged = lds + (size_t)N * (TP + 1) * sizeof(double);
   const size_t staged_z = lds + (size_t)N * std::max(TP + 1, TP + dPHI) * sizeof(double);
-  return staged_z <= kLdsCu ? PhiPlan{staged_z, kPhiStageEta | kPhiStageZ}
-                            : (staged <= kLdsCu ? PhiPlan{staged, kPhiStageEta} : PhiPlan{lds, 0});
+  if (!(stage_mask & kPhiStageEta)) stage_mask = 0;
+  if (staged_z <= kLdsCu && (stage_mask & kPhiStageZ)) return PhiPlan{staged_z, kPhiStageEta | kPhiStageZ};
+  if (staged <= kLdsCu && (stage_mask & kPhiStageEta)) return PhiPlan{staged, kPhiStageEta};
+  return PhiPlan{lds, 0};
 }
-hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs);
+hipError_t launch_phi(hipStream_t st, Dims d, const int* Tslot, int dPHI, const double* sPHIall, ChainState cs,
+                      int phi_stage);
 
 // the untemplated kernels: one thread per element (k_store: a fixed 64 x B grid; the self-tests: one wave per probe)
 hipError_t launch_sv_mix(hipStream_t st, Dims d, const int* Tslot, ChainState cs, RngArgs ra);

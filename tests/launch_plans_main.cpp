@@ -9,6 +9,7 @@
 //   oct elbTmax Ns             -> the same for k_elb_gibbs_oct
 //   draw1 W elbTmax nmax res   -> the same for k_ps_draw1
 //   misc N K KP TP dPHI        -> n_bucket, the A-step and PHI plans, whether the other kernels' LDS fits a CU
+//   phi N TP dPHI mask         -> the LDS bytes and stage bits launch_phi takes with option phi_stage = mask
 //   fcst N p H bh reg_opt      -> fcst_reg_path, fcst_chunk (register form, LDS form), the k_fcst<RN> instance and the
 //                                 chunk and LDS bytes launch_fcst takes with option fcst_reg = reg_opt (Kx = N p + 1)
 //   girf N p Ny generic        -> girf_plan: fast NY4 (-1: table-driven), k_girf<KS> bucket, nks, threads, LDS bytes
@@ -71,6 +72,9 @@ int main() {
                         resid_multi_lds_bytes(a, b) <= kLdsCu),
                   (int)(fcst_scores_lds_doubles(a) * sizeof(double) <= kLdsCu),
                   (int)(sl_lds_bytes(1, d + 8, a + 1, d, n_bucket(a)) <= kLdsCu));
+    } else if (!std::strcmp(cmd, "phi") && std::scanf("%d %d %d %d", &a, &b, &c, &d) == 4) {
+      const PhiPlan ph = phi_plan(a, b, c, d);
+      std::printf("%zu %d\n", ph.lds, ph.stage_eta);
     } else if (!std::strcmp(cmd, "fcst") && std::scanf("%d %d %d %d %d", &a, &b, &c, &d, &e) == 5) {
       const int Kx = a * b + 1;
       const bool reg = fcst_reg_path(a, b, d) && e;

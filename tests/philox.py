@@ -58,3 +58,15 @@ def girf_normals(seed, M, N, H, nsim):
     i, h, nn, m = np.meshgrid(np.arange(N), np.arange(H), np.arange(nsim), np.arange(M), indexing="ij")
     idx = (nn * H + h) * N + i
     return (normal(seed, m, 0, GIRF_BLOCK_Z, idx), normal(seed, m, 0, GIRF_BLOCK_SVZ, idx))
+
+
+PHI_BLOCK = 5  # CCMM_RNG_PHI (include/ccmm.h)
+
+
+def phi_normals(seed, B, N, T, dPHI, sweep=0):
+    """The normals k_phi_gen draws for the inverse-Wishart block (csrc/ccmm_kernels.hip): block CCMM_RNG_PHI, index
+    i + N col of the N x (T + dPHI) column-major matrix, the chain as the chain word.  The block-level drop-in
+    ccmm_phi_iw with Zdraw == NULL runs seed 0 at sweep 0 (ccmm_dropins.hip: block_cfg, crn_args).  Returns Z in the
+    drop-in's layout N x (T + dPHI) x B."""
+    i, col, c = np.meshgrid(np.arange(N), np.arange(T + dPHI), np.arange(B), indexing="ij")
+    return normal(seed, c, sweep, PHI_BLOCK, i + N * col)

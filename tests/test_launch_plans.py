@@ -6,7 +6,8 @@ about the library, and against the layout comments of the kernels region by regi
 launch (fcst_reg_path, fcst_chunk, fcst_variant, fcst_paths_lds_doubles) is checked on every case of
 tests/fcst_cases.py in the same way, and the GIRF launch (ccmm_girf.h girf_plan, girf_lds, girf_fast_lds) on every
 case of tests/girf_cases.py.  The large-N path (ccmm_bign.h: the padded Gram dimension, the LDS sizes and the SV
-scratch for every N = 33..128; ccmm_big.h: big_solve_plan) is checked against tests/bign_cases.py.  The same program
+scratch for every N = 33..128; ccmm_big.h: big_solve_plan) is checked against tests/bign_cases.py, and phi_plan
+(ccmm_sweep.h) with every value of option phi_stage against tests/phi_cases.py.  The same program
 prints the library's Philox4x32-10 words (Rng::raw), which pin tests/philox.py bit for bit."""
 import subprocess
 
@@ -16,6 +17,7 @@ import bign_cases as BC
 import elb_cases as EC
 import fcst_cases as FC
 import girf_cases as GC
+import phi_cases as PC
 import philox
 from conftest import ROOT
 
@@ -146,6 +148,34 @@ def test_prep_and_sweep_plans(plans):
     assert r32[2] == -1 and r32[4] == 0 and r32[3] == 4 * 32 * 33 * 8
     assert all(r[1] <= LDS_CU and r[3] <= LDS_CU and r[5:7] == [1, 1] for r in (r20, r32, r8, r9))
     assert (r8[7], r32[7]) == (1, 0)  # the lag solve's resident design: N = 8 at TP = 96 fits, N = 32 at 768 does not
+
+
+def test_phi_plans_match_the_restatement(plans):
+    """phi_plan (ccmm_sweep.h) on every case of tests/phi_cases.py: the bytes and stage bits of the default launch
+    through the `misc` query, and those of every value of option phi_stage; the case list holds all three plans, the
+    byte boundaries sit where the cases put them, and every staging-round case lands on its round count."""
+    cases = list(PC.CASES) + [PC.MULTI[:3]]
+    for (N, T, dPHI), row in zip(cases, plans([f"misc {N} {N + 1} 64 {PC.round_up(T, 32)} {dPHI}" for N, T, dPHI in cases])):
+        lds, bits = int(row[3]), int(row[4])
+        assert (lds, bits) == PC.plan(N, T, dPHI), (N, T, dPHI)
+        assert bits == PC.CASES.get((N, T, dPHI), 3) and lds <= LDS_CU, (N, T, dPHI)
+    q = [(c, m) for c in cases for m in (0, 1, 2, 3)]
+    for ((N, T, dPHI), m), row in zip(q, plans([f"phi {N} {PC.round_up(T, 32)} {dPHI} {m}" for (N, T, dPHI), m in q])):
+        assert (int(row[0]), int(row[1])) == PC.plan(N, T, dPHI, m), (N, T, dPHI, m)
+        want = PC.plan(N, T, dPHI)[1] & m
+        assert int(row[1]) == (want if want & 1 else 0), (N, T, dPHI, m)   # Z is never staged without eta
+    assert set(PC.CASES.values()) == {0, 1, 3}
+    # to the byte: 160 KiB stages eta and Z, one double per row more does not; then eta alone to its own limit
+    assert PC.plan(32, 97, 380)[0] == PC.plan(5, 4064, 8)[0] == LDS_CU
+    assert PC.plan_bytes(32, 97, 381)[2] == LDS_CU + 32 * 8 and PC.plan_bytes(5, 4064, 9)[2] == LDS_CU + 5 * 8
+    assert PC.plan_bytes(32, 480, 35)[1] <= LDS_CU < PC.plan_bytes(32, 481, 35)[1]
+    assert PC.plan_bytes(5, 4064, 9)[1] <= LDS_CU < PC.plan_bytes(5, 4065, 8)[1]
+    assert PC.plan(20, 750, 23) == (140_000, 3)
+    # staging rounds of 4096 doubles
+    for (N, T, dPHI), (which, n, r) in PC.ROUNDS.items():
+        assert n == (N * PC.round_up(T, 32) if which == "eta" else N * (T + dPHI)), (N, T, dPHI)
+        assert PC.rounds(N, T, dPHI)[which == "z"] == r == -(-n // 4096), (N, T, dPHI)
+    assert {(w, n % 4096 == 0) for w, n, _ in PC.ROUNDS.values()} == {("eta", True), ("eta", False), ("z", True), ("z", False)}
 
 
 def test_fcst_plans_match_the_restatement(plans):

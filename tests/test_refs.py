@@ -440,3 +440,29 @@ def test_ps_cases_cover_the_edges():
     assert r1.nc - r0.nc == 1 and r0.resident and not r1.resident
     assert C["hybrid_gaps"].hybrid and sum(c.hybrid for c in C.values()) == 1
     assert {psc.CONFIGS[k][0] for k in psc.CONFIGS} == {1, psc.BLOCK, psc.BLOCK + 1, 600}
+
+
+# ================================================================================================================
+# The PHI draw for N <= 32 (tests/phi_cases.py, tests/test_gpu_phi_edges.py: the device within 1e-11 of
+# refs.phi_iw_ld relative to the largest entry).  The fp64 oracle under the bound of
+# test_bign_phi_oracle_vs_longdouble on every case, every chain of the 33-chain case included.  Measured worst:
+# 6.2e-15 (N = 5, T = 4064, dPHI = 8).
+import phi_cases as phc  # noqa: E402
+
+
+@pytest.mark.parametrize("N,T,dPHI", list(phc.CASES))
+def test_phi_oracle_vs_longdouble(N, T, dPHI):
+    for c, ((sq, PHI), (osq, oPHI)) in enumerate(phc.phi_reference(N, T, dPHI)):
+        e = max(phc.phi_err(osq, oPHI, sq, PHI))
+        print(f"phi N={N} T={T} dPHI={dPHI} chain {c}: oracle vs longdouble {e:.2e}")
+        assert e < 1e-12, e  # the device bound of this block is 1e-11
+
+
+def test_phi_multi_oracle_vs_longdouble():
+    orc, ld = phc.multi_reference()
+    assert len(orc) == phc.MULTI[3] and sorted(ld) == list(phc.MULTI_LD_CHAINS)
+    for c, (sq, PHI) in ld.items():
+        e = max(phc.phi_err(*orc[c], sq, PHI))
+        print(f"phi multi chain {c}: oracle vs longdouble {e:.2e}")
+        assert e < 1e-12, e
+    assert not np.array_equal(orc[0][1], orc[32][1])
