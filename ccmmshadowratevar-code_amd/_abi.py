@@ -162,6 +162,11 @@ _SIGS = {
     "ccmm_max_var_root_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_max_var_root": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_chains_max_var_roots": (C.c_int, [C.c_void_p, C.c_int, _dp, _ip]),
+    "ccmm_vma_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
+    "ccmm_vma": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
+    "ccmm_vma_form": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _dp]),
+    "ccmm_chains_vma_summaries": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                            _dp, _dp, _ip]),
     "ccmm_diagnostics_host": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, _dp, _dp]),
     "ccmm_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "ccmm_chains_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
@@ -296,6 +301,22 @@ def max_var_root_host(PAI_all, N, p, return_info=False):
     info = np.zeros(M, dtype=np.int32)
     _check(load_library().ccmm_max_var_root_host(M, int(N), int(p), K, _ptr(P), _ptr(out), _ptr(info, _ip)),
            "ccmm_max_var_root_host")
+    return (out, info) if return_info else out
+
+
+def _vma_out(M, N, H):
+    """N x N x H x M in MATLAB (column-major) order, and its info."""
+    return np.zeros((N, N, H, M), order="F"), np.zeros(M, dtype=np.int32)
+
+
+def vma_host(PAI_all, N, p, H, return_info=False):
+    """ccmm_vma_host: drawsVMA(:,:,h,m) = (comp^h)(1:N,1:N), h = 1..H, of each PAI (M x K x N), by the
+    library's fp64 recursion on the CPU (at most 16 threads; no GPU needed).  Returns N x N x H x M; info per
+    matrix: 0, or 1 for non-finite coefficients (the matrix's responses are all NaN)."""
+    M, K, P = _pai_batch(PAI_all, N, p)
+    out, info = _vma_out(M, int(N), int(H))
+    _check(load_library().ccmm_vma_host(M, int(N), int(p), K, int(H), _ptr(P), _ptr(out), _ptr(info, _ip)),
+           "ccmm_vma_host")
     return (out, info) if return_info else out
 
 
@@ -656,6 +677,25 @@ class Context:
                "ccmm_max_var_root")
         return (out, info) if return_info else out
 
+    def vma(self, PAI_all, N, p, H, return_info=False):
+        """ccmm_vma: as vma_host, on the device for N <= 32 and N p <= 256 (the kernel k_vma, bit-identical to
+        vma_host), on the CPU otherwise."""
+        M, K, P = _pai_batch(PAI_all, N, p)
+        out, info = _vma_out(M, int(N), int(H))
+        _check(self.lib.ccmm_vma(self.handle, M, int(N), int(p), K, int(H), _ptr(P), _ptr(out), _ptr(info, _ip)),
+               "ccmm_vma")
+        return (out, info) if return_info else out
+
+    def vma_form(self, form, PAI_all, N, p, H):
+        """ccmm_vma_form: as vma on the device range, by kernel form 0 (MFMA) or 1 (vector ALU; the same bits).
+        Returns (N x N x H x M, device milliseconds of the kernel launches alone)."""
+        M, K, P = _pai_batch(PAI_all, N, p)
+        out, info = _vma_out(M, int(N), int(H))
+        ms = C.c_double(0.0)
+        _check(self.lib.ccmm_vma_form(self.handle, int(form), M, int(N), int(p), K, int(H), _ptr(P), _ptr(out),
+                                      _ptr(info, _ip), C.byref(ms)), "ccmm_vma_form")
+        return out, float(ms.value)
+
     def diagnostics(self, draws):
         """ccmm_diagnostics: as diagnostics_host, by the kernel k_diag_series on the device (the same bits)."""
         d = np.asfortranarray(_diag_draws(draws))
@@ -800,7 +840,7 @@ class Chains:
                "k_elb_prep", "k_elb_cond", "k_elb_gibbs", "k_elb_rebuild", "k_gram_chol_lag",
                "k_cta_solve_lag", "k_fcst", "k_gram_big", "k_chol_big", "k_cta_solve_big",
                "k_astep_big", "k_sv_big", "k_phi_big", "k_ps_chol", "k_ps_prop", "k_eig_maxroot",
-               "k_stat_select", "k_diag_series")
+               "k_stat_select", "k_diag_series", "k_vma", "k_sum_ffr", "k_gather_pai", "k_post_stats")
 
     def __init__(self, ctx: Context, *, N, p, T, B, ndata=1, model=MODEL_LINEAR, crn=False,
                  store_capacity=0, logy2offset=1e-3, seed=1012023, dPHI=None, Ns=0, elbTmax=0,
@@ -977,6 +1017,28 @@ class Chains:
         nC = _check(self.lib.ccmm_chains_max_var_roots(self.handle, int(slot), _ptr(out), _ptr(info, _ip)),
                     "ccmm_chains_max_var_roots")
         return (out[:st * nC], info[:st * nC]) if return_info else out[:st * nC]
+
+    def vma_summaries(self, slot, H, pct, ffr=None, hslab=0):
+        """ccmm_chains_vma_summaries: VMAmid / VMAtail (goVARshadowrateBlockHybrid.m:409-414) of the stored PAI
+        draws of the chains bound to ``slot``, read in place and pooled over its chains: dict with median
+        (N x N x H) and quantiles (N x N x H x nq).  ffr (0-based variable) adds sumMedian (N) and sumQuantiles
+        (N x nq), the same statistics of the sum over lags of that variable's coefficients (:416-429).  hslab:
+        horizons per pass (0: the most within 1 GB per buffer); the results do not depend on it.  Raises
+        RuntimeError when a stored draw holds a NaN or Inf coefficient.  The store is kept."""
+        N, H = self.N, int(H)
+        pct = _f(np.asarray(pct, float).ravel())
+        nq = pct.size
+        out = dict(median=np.zeros((N, N, H), order="F"), quantiles=np.zeros((N, N, H, nq), order="F"))
+        if ffr is not None:
+            out.update(sumMedian=np.zeros(N), sumQuantiles=np.zeros((N, nq), order="F"))
+        nbad = C.c_int(0)
+        _check(self.lib.ccmm_chains_vma_summaries(
+            self.handle, int(slot), H, int(hslab), nq, _ptr(pct) if nq else None, _ptr(out["median"]),
+            _ptr(out["quantiles"]) if nq else None, -1 if ffr is None else int(ffr), _ptr(out.get("sumMedian")),
+            _ptr(out.get("sumQuantiles")) if nq else None, C.byref(nbad)), "ccmm_chains_vma_summaries")
+        if nbad.value > 0:
+            raise RuntimeError(f"ccmm_chains_vma_summaries: {nbad.value} stored draws hold a NaN or Inf coefficient")
+        return out
 
     DIAG_SOURCES = {"PAI": 0, "PHI": 1, "invA": 2, "sqrtht": 3, "shadowrate": 4}
 

@@ -2,7 +2,8 @@
 // methods' declarations.  The bodies are in the unit of their block: ccmm_chains.hip (set-up, data, state,
 // exports, profile), ccmm_chains_sweep.hip (the Gibbs blocks of a sweep), ccmm_chains_elb.hip (ELB step,
 // PS branch, treatment), ccmm_chains_fcst.hip (predictive density, summaries), ccmm_chains_eig.hip (maximum VAR
-// roots, check_stationarity), ccmm_chains_diag.hip (Compute_diagnostics of the stored draws).
+// roots, check_stationarity), ccmm_chains_diag.hip (Compute_diagnostics of the stored draws), ccmm_chains_vma.hip
+// (impulse responses of the stored draws and their summaries).
 #pragma once
 #include "ccmm_host.h"
 #include "ccmm_sweep.h"
@@ -195,6 +196,12 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   DBuf<double> diagOut;
   DBuf<uint8_t> diagMask;
   DBuf<int> diagCnt;
+
+  // ---------------------------------------------------------------- impulse responses
+  // ccmm_chains_vma.hip: the draw-major responses of one horizon slab (k_vma) and the screen's flag per draw;
+  // the segments and the sorted copy are postA / postB
+  DBuf<double> vmaBuf;
+  DBuf<int> vmaInfo;
 
   // ---------------------------------------------------------------- profiling
   bool profiling = false;

@@ -106,6 +106,10 @@ enum KernelId {
   KID_EIG,
   KID_STATSEL,
   KID_DIAG,
+  KID_VMA,
+  KID_SUMFFR,
+  KID_POSTGATHER,
+  KID_POSTSTATS,
   KID_COUNT
 };
 extern const char* const kKernelNames[KID_COUNT];  // ccmm_chains.hip

@@ -712,11 +712,21 @@ def max_var_roots(PAI_all, N, p, threads=16, device=None):
         return np.array(list(ex.map(one, [PAI_all[m] for m in range(M)])))
 
 
+def VMA(PAI_all, N, p, H, *, device=None):
+    """drawsVMA of goVARshadowrateBlockHybrid.m:397-408: (comp^h)(1:N, 1:N), h = 1..H, of every draw's companion
+    matrix, PAI_all M x K x N (K >= 1 + N p; the intercept and any further rows are ignored).  Returns
+    N x N x H x M.  device=None: the library's host function (ccmm_vma_host, no GPU needed); device=d: its
+    kernel on HIP device d (Context.vma; the same bits)."""
+    if device is not None:
+        return context(int(device)).vma(PAI_all, N, p, H)
+    return _abi.vma_host(PAI_all, N, p, H)
+
+
 def save_qrt_mat(filename, res, *, data, ydates, p, ncode, tcode, cumcode, ndxSHADOWRATE,
                  ndxOTHERYIELDS, ELBbound, actualrateBlock, datalabel, modellabel, MCMCdraws,
                  fcstNhorizons, doQuarterly=False):
     """The QRT summary file of goVARshadowrateBlockHybrid.m:641-669 (varlist: data, ydates, p,
-    Tjumpoffs, N, ncode, tcode, cumcode, fcst*, fcstNhorizons, PAI*, shadowrate*, missingrate*,
+    Tjumpoffs, N, ncode, tcode, cumcode, fcst*, fcstNhorizons, PAI*, shadowrate*, missingrate*, VMA*, sumFFR*,
     ndx*, ELBbound, ELBdummy, actualrateBlock, datalabel, modellabel, doQuarterly,
     setQuantiles, MCMCdraws) from a goVARshadowrateBlockHybrid_batch result.  MATLAB
     -v7.3 is HDF5; this writes the same names and shapes as a v5 MAT-file (scipy.io.savemat).
@@ -743,7 +753,7 @@ def save_qrt_mat(filename, res, *, data, ydates, p, ncode, tcode, cumcode, ndxSH
              missingrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
     for k, v in res.items():
         # the reference's wildcards; shadowratePSRFchains (psrf across chains) is not a reference output
-        if k.startswith(("fcst", "PAI", "shadowrate")) and k != "shadowratePSRFchains" and isinstance(v, np.ndarray):
+        if k.startswith(("fcst", "PAI", "shadowrate", "VMA", "sumFFR")) and k != "shadowratePSRFchains" and isinstance(v, np.ndarray):
             m[k] = v[None, :] if v.ndim == 1 else v
     savemat(filename, m, do_compression=True)
     return sorted(m)
@@ -847,10 +857,12 @@ class _Field(NamedTuple):
     name: str
     src: str            # a device summary (Chains.summaries) of the vintage's kept draws: pa PAI, yd ydraws, yc
     #                     ycumdraws, yz ycensordraws (shadow-rate VAR), sh shadowratedraws; or scores / logscore
-    #                     (the one-step score draws, their log mean exp), ycr (cumulated yrealized), host
+    #                     (the one-step score draws, their log mean exp), ycr (cumulated yrealized), host; vm:
+    #                     Chains.vma_summaries of the vintage's stored draws
     stat: object        # of a summary: mean, stdev, median, quantiles, crps; of the scores: their column
     shape: tuple        # in terms of K, N, H, Ny, nq, Ns, nd = fcstNdraws C, nr = MCMCdraws C
-    need: str = ""      # p: with postprocess; f: model with linear_fcst; l: with maxlambda
+    need: str = ""      # p: with postprocess; f: model with linear_fcst; l: with maxlambda; v: doLoMem=False;
+    #                     s: with a policy-rate variable for sumFFR
     fill: float = np.nan
 
 
@@ -877,6 +889,8 @@ _FIELDS = (
     _Field("fcstYcensormedian", "yz", "median", ("N", "H"), "pf"), _Field("fcstYcensorcrps", "yz", "crps", ("N", "H"), "pf"),
     _Field("fcstYcensorquantiles", "yz", "quantiles", ("N", "H", "nq"), "pf"),
     _Field("drawsMaxVARroot", "host", None, ("nr",), "l"),
+    _Field("VMAmid", "vm", "median", ("N", "N", "H"), "v"), _Field("VMAtail", "vm", "quantiles", ("N", "N", "H", "nq"), "v"),
+    _Field("sumFFRmid", "vm", "sumMedian", ("N",), "vs"), _Field("sumFFRtail", "vm", "sumQuantiles", ("N", "nq"), "vs"),
 )
 
 # forecast errors taken at the end of the run where both terms are there: name, realized, forecast
@@ -889,9 +903,10 @@ _ERROR_FIELDS = (("fcstYhaterror", "fcstYrealized", "fcstYhat"),
                  ("fcstYcummederror", "fcstYcumrealized", "fcstYcummedian"))
 
 
-def _fields(postprocess, linear_fcst, maxlambda):
+def _fields(postprocess, linear_fcst, maxlambda, vma=False, sumffr=False):
     """The rows of _FIELDS that a run with these switches fills."""
-    have = ("p" if postprocess else "") + ("f" if linear_fcst else "") + ("l" if maxlambda else "")
+    have = ("p" if postprocess else "") + ("f" if linear_fcst else "") + ("l" if maxlambda else "") + \
+        ("v" if vma else "") + ("s" if sumffr else "")
     return [f for f in _FIELDS if set(f.need) <= set(have)]
 
 
@@ -1008,9 +1023,10 @@ def _vintage_summaries(ch, b, k, yr, yields):
     return q
 
 
-def _vintage_result(b, acc, k, unit, q, diag):
+def _vintage_result(b, acc, k, unit, q, diag, vm=None):
     """The result dict of the vintage in data slot k (chains k C .. (k + 1) C - 1 of ``acc``), under the names
-    of _FIELDS; q: its _vintage_summaries or None, diag: its _chain_diagnostics or {}."""
+    of _FIELDS; q: its _vintage_summaries or None, diag: its _chain_diagnostics or {}, vm: its
+    Chains.vma_summaries or None."""
     thisT, bm, yr = unit
     C, N, H, K, Ns, ndxY = b.C, b.N, b.H, b.K, b.Ns, b.ndxYIELDS
     cs = slice(k * C, (k + 1) * C)
@@ -1033,8 +1049,10 @@ def _vintage_result(b, acc, k, unit, q, diag):
         if b.cumcode is not None:
             yh[b.cumcode] = np.cumsum(yh[b.cumcode], axis=1)                # :355
         r["fcstYcumhat"] = yh
-    for f in _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda):
-        if f.src == "logscore":
+    for f in _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda, b.vma, b.ffr is not None):
+        if f.src == "vm":
+            r[f.name] = vm[f.stat]
+        elif f.src == "logscore":
             r[f.name] = _logmeanexp(scores[:, :, f.stat, cs].ravel())
         elif f.src == "scores":
             r[f.name] = scores[:, :, f.stat, cs].ravel(order="F")
@@ -1097,6 +1115,11 @@ def _batch_attempt(b, vidx, attempt):
             post[i] = _vintage_summaries(ch, b, k, us[k][2], yields)
             if k % 8 == 7 or k == len(vidx) - 1:
                 _say(b, f"device summaries {k + 1}/{len(vidx)} vintages")
+    vma = {}
+    if b.vma:  # the ~doLoMem block (:393-429) on the stored draws, before get_draws empties the store
+        for k, i in enumerate(vidx):
+            vma[i] = ch.vma_summaries(k, b.H, b.pct, ffr=b.ffr)
+        _say(b, f"impulse-response summaries of {len(vidx)} vintages")
     if b.hold:
         if b.diagnostics:  # Diagnostics.m on the stored draws, before get_draws empties the store
             for k, i in enumerate(vidx):
@@ -1112,7 +1135,7 @@ def _batch_attempt(b, vidx, attempt):
         if np.any(acc.status[k * C:(k + 1) * C] & ~_abi.STATUS_INFO):  # bits 1, 64: informational (valid draws)
             failed.append(i)
             continue
-        res[mine[i]] = _vintage_result(b, acc, k, us[k], post.get(i), diag.get(i, {}))
+        res[mine[i]] = _vintage_result(b, acc, k, us[k], post.get(i), diag.get(i, {}), vma.get(i))
         if k % 4 == 3 or k == len(vidx) - 1:
             _say(b, f"results {k + 1}/{len(vidx)} vintages")
     return res, failed
@@ -1123,7 +1146,7 @@ def _batch_out(b, allv, Tjumpoffs, assignment, Tdata, jumpoff):
     with the vintage last, by _FIELDS, then the forecast errors."""
     V, Ns = len(Tjumpoffs), b.Ns
     out = dict(Tjumpoffs=np.array(Tjumpoffs), assignment=assignment)
-    fields = _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda)
+    fields = _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda, b.vma, b.ffr is not None)
     for f in fields:
         out[f.name] = np.full(tuple(b.dims[d] for d in f.shape) + (V,), f.fill)
     windows = ("shadowrate",) + (("missingrate",) if b.spec.linear_fcst or b.missing else ())
@@ -1167,7 +1190,8 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                                      Nproposals=_MODELS["blockhybrid"].Nproposals, elb_ps=True, postprocess=False, cumcode=None,
                                      setQuantiles=None, maxlambda=False, model="blockhybrid",
                                      engine="python", doELBsampling=True, check_stationarity=0,
-                                     engine_roots="device", Compute_diagnostics=False):
+                                     engine_roots="device", Compute_diagnostics=False, doLoMem=True,
+                                     sumFFRndx=None):
     """The quasi-real-time OOS run of goVARshadowrateBlockHybrid.m:126-517 for the block-
     hybrid shadow-rate VAR, as ONE device-resident chain set per rank: every vintage
     thisT in Tjumpoffs (default: ydates > 2008-12, :127) is a data slot of the set with
@@ -1247,12 +1271,30 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     diagPAIif, diagInvAif, diagPHIif (3 x V), each the per-chain value averaged over the vintage's chains (the
     convention of shadowratePSRF).  Every kept draw then stays in the store (store_capacity = MCMCdraws, as
     with postprocess) and Chains.diagnostics reads it in place before it is downloaded; the draws themselves do
-    not change.  MCMCdraws < 100 raises momentg's error before anything runs.  Python engine only."""
+    not change.  MCMCdraws < 100 raises momentg's error before anything runs.  Python engine only.
+
+    doLoMem=False (the reference's name and default True; the ``~doLoMem`` block of :393-429) adds the posterior
+    impulse-response bands per vintage: VMAmid (N x N x H x V) and VMAtail (N x N x H x nq x V), the median and the
+    setQuantiles percentiles over the vintage's kept draws (pooled over its chains) of drawsVMA(:,:,h,m) =
+    (comp^h)(1:N,1:N), h = 1..fcstNhorizons, and sumFFRmid (N x V) / sumFFRtail (N x nq x V), the same of the sum
+    over lags of the policy-rate coefficients of each equation.  All on the device from the stored draws
+    (Chains.vma_summaries; N <= 32 and N p <= 256), so the store holds every kept draw as with postprocess; the
+    draws themselves do not change.  The policy rate is ndxSHADOWRATE when it names one variable; with none
+    sumFFR* are omitted, as in the reference; with several the reference's ndxFFRcoef(i) = (i-1)*N + ndxSHADOWRATE
+    stops with an assignment error, so there is no behaviour to follow and ValueError is raised unless
+    sumFFRndx=<one 0-based variable> (FEDFUNDS, say) names it.  Refused by engine="native" (ccmm_batch_config is
+    frozen) and by model="hybrid" (goVARhybrid.m:382-430 has the block commented out)."""
     from . import distributed as dm
     _check_diag_draws(Compute_diagnostics, MCMCdraws)
     if Compute_diagnostics and engine == "native":
         raise ValueError("Compute_diagnostics runs on the Python engine (engine='python'): "
                          "ccmm_batch_config carries no field for it")
+    vma = not doLoMem
+    if vma and engine == "native":
+        raise ValueError("doLoMem=False runs on the Python engine (engine='python'): "
+                         "ccmm_batch_config carries no field for it")
+    if vma and model == "hybrid":
+        raise ValueError("goVARhybrid.m computes no impulse responses (:382-430 commented out)")
     missing = not doELBsampling
     if missing and engine == "native":
         raise ValueError("doELBsampling=False runs on the Python engine (engine='python'): "
@@ -1295,6 +1337,20 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         warnings.warn("no stationarity check for hybrid model")          # mcmcVARhybridGibbs.m:22-24
         check_stationarity = 0
     Ns = ndxSHADOWRATE.size
+    ffr = None
+    if vma:
+        if N > 32 or N * p > 256:
+            raise ValueError("doLoMem=False: the device summaries serve N <= 32 and N p <= 256")
+        if sumFFRndx is not None:
+            ffr = int(sumFFRndx)
+            if not 0 <= ffr < N:
+                raise ValueError(f"sumFFRndx must be one 0-based variable index below N = {N}")
+        elif Ns == 1:
+            ffr = int(ndxSHADOWRATE[0])
+        elif Ns > 1:
+            raise ValueError("doLoMem=False with several shadow rates: the reference's ndxFFRcoef(i) = (i-1)*N + "
+                             "ndxSHADOWRATE stops with an assignment error, so sumFFR has no defined variable; "
+                             "name it with sumFFRndx=<one 0-based index>")
     K = N * p + 1 + (Ns * p if spec.ffr_lags else 0)
     costs = [dm.unit_cost(t - p, K, N, n_cens=dm.censored_months(data0, ndxSHADOWRATE, ELBbound, startELB, t)) * C
              for t in Tjumpoffs]
@@ -1309,7 +1365,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     pct = np.asarray(SET_QUANTILES if setQuantiles is None else setQuantiles, float)
     # postprocess (and the shadow-rate VAR, whose yhat needs the floored draws): every kept draw and forecast
     # path stays on the device until the per-vintage summaries (ccmm_chains_summaries) have been taken; with
-    # them or Compute_diagnostics the store holds every kept draw until the end of the attempt
+    # them, Compute_diagnostics or doLoMem=False the store holds every kept draw until the end of the attempt
     dev = bool(postprocess or spec.linear_fcst)
     b = SimpleNamespace(                                 # what the steps of a run share; fixed over the attempts
         model=model, spec=spec, ctx=ctx, units=units, mine=mine, rank=rank, progress=progress,
@@ -1318,7 +1374,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         Nproposals=Nproposals, elb_ps=elb_ps, missing=missing, check_stationarity=check_stationarity,
         postprocess=postprocess, pct=pct, cumcode=None if cumcode is None else np.asarray(cumcode, bool),
         keep_draws=keep_draws, maxlambda=maxlambda, dev_roots=maxlambda and engine_roots == "device",
-        diagnostics=bool(Compute_diagnostics), dev=dev, hold=dev or bool(Compute_diagnostics),
+        diagnostics=bool(Compute_diagnostics), dev=dev, hold=dev or bool(Compute_diagnostics) or vma, vma=vma, ffr=ffr,
         ndxYIELDS=ndxYIELDS, smask=_mask(N, ndxSHADOWRATE), startELB=startELB,
         elbdummy=data0[:, ndxSHADOWRATE] <= ELBbound,                    # ELBdummy, :131
         dims=dict(K=K, N=N, H=H, Ny=ndxYIELDS.size, nq=pct.size, Ns=Ns, nd=fcstNdraws * C, nr=MCMCdraws * C),

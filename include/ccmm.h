@@ -549,6 +549,41 @@ int ccmm_max_var_root(ccmm_ctx* ctx, int M, int N, int p, int K, const double* P
  * left as it is. */
 int ccmm_chains_max_var_roots(ccmm_chains* ch, int slot, double* maxroot, int* info);
 
+/* ------------------------------------------------------------ impulse responses (VMA)
+ * drawsVMA(:,:,h,m) = (comp^h)(1:N,1:N), h = 1..H, of each of M coefficient matrices
+ * (goVARshadowrateBlockHybrid.m:393-408), PAI as for the maximum root (K x N column-major, K >= 1 + N p; the
+ * intercept row and the rows beyond 1 + N p are ignored).  Computed as the recursion
+ * Psi_h = sum_l Phi_l Psi_{h-l} (Psi_0 = I, Phi_l = PAI(1 + (l-1) N + (1:N), :)'), the as-written product with
+ * its exact zeros removed, in fp64 with one fused multiply-add chain per element (lags ascending, columns
+ * ascending within a lag).  vma: N x N x H x M doubles in MATLAB order (vma[((m H + h-1) N + j) N + i] =
+ * Psi_h(i, j) of matrix m).  info: M ints, 0, or 1 for a NaN or Inf among the N p x N coefficients; may be
+ * NULL.  A matrix with info = 1 is NaN in every entry of every horizon; the reference's product gives NaN (or
+ * keeps finite entries) at h = 1 where the non-finite coefficient does not reach and NaN everywhere from
+ * h = 2 on: h = 1 is the one documented difference. */
+/* On the CPU (at most 16 threads); needs no context and no GPU. */
+int ccmm_vma_host(int M, int N, int p, int K, int H, const double* PAI, double* vma, int* info);
+/* Host PAI, uploaded in chunks; on the device for N <= 32 and N p <= 256 (one workgroup per matrix on the FP64
+ * MFMA, bit-identical to the host function), on the CPU for any larger shape. */
+int ccmm_vma(ccmm_ctx* ctx, int M, int N, int p, int K, int H, const double* PAI, double* vma, int* info);
+/* As ccmm_vma on the device range only, with the kernel form chosen: 0 the MFMA product (ccmm_vma's), 1 the
+ * same chains on the vector ALU (the same bits); kernel_ms (or NULL): the device time of the kernel launches
+ * alone.  The comparison entry of tools/probe_vma.py. */
+int ccmm_vma_form(ccmm_ctx* ctx, int form, int M, int N, int p, int K, int H, const double* PAI, double* vma,
+                  int* info, double* kernel_ms);
+/* VMAmid / VMAtail and sumFFRmid / sumFFRtail (:409-429) of the stored PAI draws of the chains bound to data
+ * slot `slot` (contiguous chain indices), read in place and pooled over the slot's C chains (stored x C draws):
+ * per slab of horizons the responses of every draw (draw-major), their transposition into per-series segments
+ * and the median and MATLAB prctile of each series (as ccmm_chains_summaries).  hslab: horizons per slab, 0 for
+ * the most that keeps every buffer of a pass within 1 GB; the results do not depend on it.  vmaMedian: N N H;
+ * vmaQuantiles: N N H x nq, series fastest; either may be NULL.  ffr >= 0 (0-based variable; -1: none) also
+ * gives, per equation n, the statistics of sum_{l=0..p-1} PAI(1 + l N + ffr, n) (plain adds, ascending lag):
+ * sumMedian N, sumQuantiles N x nq.  nbad (or NULL): the draws with a NaN or Inf coefficient (their responses
+ * are NaN and enter the statistics as such).  N <= 32 and N p <= 256 only.  Returns C (> 0), or a negative
+ * error code.  The draw store is left as it is. */
+int ccmm_chains_vma_summaries(ccmm_chains* ch, int slot, int H, int hslab, int nq, const double* pct,
+                              double* vmaMedian, double* vmaQuantiles, int ffr, double* sumMedian,
+                              double* sumQuantiles, int* nbad);
+
 /* check_stationarity (mcmcVAR.m:221-232, mcmcVARshadowrateBlockHybrid.m:333-347): with enable != 0 every
  * sweep computes the maximum VAR root of each chain's new PAI after the coefficient block and, while a chain's
  * root is >= 1 (or not finite), draws its coefficient block again from the rejected PAI with fresh normals; the

@@ -88,7 +88,8 @@ def main():
         "reference_varlist": "goVARshadowrateBlockHybrid.m:645-655 (data, ydates, p, Tjumpoffs, N, ncode, tcode, "
                              "cumcode, fcst*, fcstNhorizons, PAI*, shadowrate*, missingrate*, ndxSHADOWRATE, "
                              "ndxYIELDS, ndxOTHERYIELDS, ELBbound, ELBdummy, actualrateBlock, datalabel, modellabel, "
-                             "doQuarterly, setQuantiles, MCMCdraws); doLoMem = true (:59) drops sumFFR* / VMA*",
+                             "doQuarterly, setQuantiles, MCMCdraws); doLoMem = true (:59) drops sumFFR* / VMA* "
+                             "(doLoMem=False of the batch drivers adds them)",
     }
     if "drawsMaxVARroot" in res:
         mx = res["drawsMaxVARroot"]
