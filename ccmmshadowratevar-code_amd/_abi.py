@@ -183,6 +183,9 @@ _SIGS = {
     "ccmm_fcst": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
                             _dp, _dp, _dp, _dp, _u8p, C.c_double, _dp, _dp, C.c_uint64,
                             C.c_int, _dp, _dp, _dp, _dp, _ip]),
+    "ccmm_fcst_big": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                _dp, _dp, _dp, _dp, _u8p, C.c_double, _dp, _dp, C.c_uint64,
+                                C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "ccmm_fcst_irf1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp,
                                  _dp, _dp, _dp, _dp, _u8p, C.c_double, _dp, _dp, C.c_uint64,
                                  C.c_int, _dp, _dp, _dp, _dp, _ip, C.c_double, _dp, _dp]),
@@ -594,6 +597,14 @@ class Context:
         return self._fcst(None, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
                           fcstNhorizons, Ndraws, svz, z, seed, sweep)
 
+    def fcst_big(self, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
+                 fcstNhorizons, Ndraws, svz=None, z=None, seed=0, sweep=0):
+        """``fcst`` on the kernels of the large-N path (ccmm_fcst_big): 1 <= N <= 128, K = N*p + 1 <= 1536.
+        Same arguments and returns; the same normals in Philox mode; the outputs agree with ``fcst`` to
+        rounding (other summation order)."""
+        return self._fcst(None, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
+                          fcstNhorizons, Ndraws, svz, z, seed, sweep, big=True)
+
     def fcst_irf1(self, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
                   fcstNhorizons, Ndraws, IRF1scale, svz=None, z=None, seed=0, sweep=0):
         """``fcst`` with the doIRF1 simulations of mcmcVARshadowrate.m:588-605 (ccmm_fcst_irf1): the linear
@@ -604,8 +615,9 @@ class Context:
                           fcstNhorizons, Ndraws, svz, z, seed, sweep)
 
     def _fcst(self, irf1scale, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, ELBbound,
-              fcstNhorizons, Ndraws, svz, z, seed, sweep):
-        what = "ccmm_fcst" if irf1scale is None else "ccmm_fcst_irf1"
+              fcstNhorizons, Ndraws, svz, z, seed, sweep, big=False):
+        """big: ccmm_fcst_big (which has no IRF form: irf1scale None)."""
+        what = "ccmm_fcst_big" if big else ("ccmm_fcst" if irf1scale is None else "ccmm_fcst_irf1")
         PAI = _f(PAI)
         K, N = PAI.shape[:2]
         B = PAI.shape[2] if PAI.ndim == 3 else 1
@@ -627,7 +639,9 @@ class Context:
                 int(seed), int(sweep), _ptr(fY), _ptr(fYc), _ptr(yhat),
                 _ptr(sc), _ptr(st, _ip)]
         out = [fY, fYc, yhat, sc, st]
-        if irf1scale is None:
+        if big:
+            rc = self.lib.ccmm_fcst_big(*args)
+        elif irf1scale is None:
             rc = self.lib.ccmm_fcst(*args)
         else:
             out += [np.zeros((N, H, Nd, B), order="F"), np.zeros((N, H, Nd, B), order="F")]

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "ccmm_chains.h"
+#include "ccmm_fcst_big.h"
 #include "ccmm_post.h"
 
 using namespace ccmm;
@@ -14,12 +15,17 @@ void ccmm_chains::set_fcst(int H, int Nd, const uint8_t* ndxYields, int keep) {
   require(cfg.p >= 1 && (cfg.K == N * p + 1 || (hybrid && cfg.K == N * p + 1 + cfg.Ns * p)),
           "predictive density needs K = N*p + 1 (hybrid: + Ns*p)");
   require(!hybrid || cfg.Ns <= kElbNsMax, "hybrid predictive density: Ns <= 5");
-  require(N <= kFcstMaxN, "predictive density supports N <= 32");
+  // N > 32: the large-N unit (ccmm_fcst_big.hip), which serves the linear and block-hybrid forms
+  require(!hybrid || N <= kFcstMaxN, "hybrid predictive density supports N <= 32");
+  require(N <= kFcstBigMaxN, "predictive density supports N <= 128");
   require(H >= 1 && Nd >= 1, "H and Nd must be >= 1");
   require(cfg.store_capacity > 0, "predictive density needs store_capacity > 0 (one record per kept draw)");
   int nwx = 0;
   for (int i = 0; i < N; ++i) nwx += ndxYields[i] ? 0 : 1;
   require(nwx > 0 && nwx < N, "need at least one macro series and one yield");
+  require(N > kFcstMaxN ? fcst_big_plan(N, p, H, Nd, fcst_bh ? 1 : 0).ok
+                        : fcst_paths_lds_doubles(N, cfg.K, p, fcst_chunk(N, cfg.K, p, H)) * sizeof(double) <= kLdsCu,
+          "forecast state does not fit LDS");
   if (bh && !hybrid)
     for (int i = 0; i < N; ++i)
       require(!(hActual[i] && ndxYields[i]), "a yield cannot be in the actual-rate block");
@@ -51,8 +57,6 @@ void ccmm_chains::set_fcst(int H, int Nd, const uint8_t* ndxYields, int keep) {
     fPaths.alloc(B * cap * Nd * HN);
     fPathsC.alloc(B * cap * Nd * HN);
   }
-  require(fcst_paths_lds_doubles(N, cfg.K, p, fcst_chunk(N, cfg.K, p, H)) * sizeof(double) <= kLdsCu,
-          "forecast state does not fit LDS");
   fSv1.alloc(B * Nd * N);
   have_fcst = true;
   have_irf = false;  // (its buffers follow H, Nd and keep_paths: ccmm_chains_set_irf1 comes after this call)
@@ -62,6 +66,7 @@ void ccmm_chains::set_fcst(int H, int Nd, const uint8_t* ndxYields, int keep) {
 
 void ccmm_chains::set_irf1(double scale, const uint8_t* cumcode) {
   const int N = cfg.N, p = cfg.p, bhf = hybrid ? 2 : (fcst_bh ? 1 : 0);
+  require(N <= kFcstMaxN, "doIRF1 supports N <= 32");
   // (the LDS form's plan, as set_fcst: no register-path shape is larger)
   require(fcst_irf_lds_doubles(N, cfg.K, p, fcst_irf_chunk(N, cfg.K, p, fH, false, bhf), false, bhf) * sizeof(double) <=
               kLdsCu,
@@ -149,7 +154,10 @@ void ccmm_chains::run_fcst(const RngArgs& ra) {
   const XSel xs = xsel();
   launch(KID_FCST, [&] {
     HIPCHECK(launch_fcst_jumpoff(fst, a, d.TP, Tslot.p, xs.ypool, xs.yidx, fXj.p));
-    HIPCHECK(launch_fcst(fst, a, fSv1.p, opt[OPT_FCST_REG] != 0));
+    if (N > kFcstMaxN)
+      HIPCHECK(launch_fcst_big(fst, a, fSv1.p));
+    else
+      HIPCHECK(launch_fcst(fst, a, fSv1.p, opt[OPT_FCST_REG] != 0));
     HIPCHECK(launch_fcst_accum(fst, a, cfg.store_capacity, fstored, (fcst_bh || hybrid) ? nullptr : fYhat.p, fYsum.p,
                                fYcsum.p, fYhatsum.p, fScStore.p, fKeep ? fPaths.p : nullptr, fKeep ? fPathsC.p : nullptr));
     if (have_irf)
@@ -422,19 +430,20 @@ int ccmm_chains_summaries_floor(ccmm_chains* ch, int source, int slot, const uin
   });
 }
 
-// ccmm_fcst (irf = false) and ccmm_fcst_irf1
+// ccmm_fcst (irf = false), ccmm_fcst_irf1 and ccmm_fcst_big (big: the large-N unit at every N <= 128)
 static int fcst_dropin(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI, const double* invA,
                        const double* logSV0, const double* sqrtPHI, const double* Xjumpoff, const double* yrealized,
                        const uint8_t* ndxYields, double elb, const double* svz, const double* z, uint64_t seed,
                        int sweep, double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status,
-                       bool irf, double irf1scale, double* fcstY1plus, double* fcstY1minus) {
+                       bool irf, double irf1scale, double* fcstY1plus, double* fcstY1minus, bool big = false) {
   return guarded([&] {
     require(!irf || (fcstY1plus && fcstY1minus), "null argument");
     require(!irf || std::isfinite(irf1scale), "IRF1scale must be finite");
     require(ctx && PAI && invA && logSV0 && sqrtPHI && Xjumpoff && yrealized && ndxYields &&
                 fcstY && fcstYcensor && yhat && scores,
             "null argument");
-    require(B > 0 && N > 0 && N <= kFcstMaxN && p > 0 && H > 0 && Nd > 0, "unsupported size");
+    require(B > 0 && N > 0 && N <= (big ? kFcstBigMaxN : kFcstMaxN) && p > 0 && H > 0 && Nd > 0, "unsupported size");
+    require(!big || (p <= kFcstBigMaxK / N && N * p + 1 <= kFcstBigMaxK), "unsupported size");
     require((svz == nullptr) == (z == nullptr), "svz and z must both be given or both NULL");
     const int K = N * p + 1;
     int nwx = 0;
@@ -443,7 +452,8 @@ static int fcst_dropin(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const 
     HIPCHECK(hipSetDevice(ctx->device));
     // (the LDS form's size even where the register path will run: it refuses no register-path shape, whose
     // largest, N = 21, p = 12 at hc = 1, is 253 * 21 + 2 * 441 + 2 * 252 + 63 = 6762 doubles, 53 KB)
-    require(fcst_paths_lds_doubles(N, K, p, fcst_chunk(N, K, p, H)) * sizeof(double) <= kLdsCu,
+    require(big ? fcst_big_plan(N, p, H, Nd, 0).ok
+                : fcst_paths_lds_doubles(N, K, p, fcst_chunk(N, K, p, H)) * sizeof(double) <= kLdsCu,
             "forecast state does not fit LDS");
     require(!irf || fcst_irf_lds_doubles(N, K, p, fcst_irf_chunk(N, K, p, H, false, 0), false, 0) * sizeof(double) <= kLdsCu,
             "forecast state does not fit LDS");
@@ -492,7 +502,10 @@ static int fcst_dropin(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const 
       a.fY1m = dfYm.p;
     }
     dsv1.alloc((size_t)B * Nd * N);
-    HIPCHECK(launch_fcst(ctx->stream, a, dsv1.p, ctx->opt[OPT_FCST_REG] != 0));
+    if (big)
+      HIPCHECK(launch_fcst_big(ctx->stream, a, dsv1.p));
+    else
+      HIPCHECK(launch_fcst(ctx->stream, a, dsv1.p, ctx->opt[OPT_FCST_REG] != 0));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
     HIPCHECK(hipMemcpy(fcstY, dfY.p, nout * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(fcstYcensor, dfYc.p, nout * sizeof(double), hipMemcpyDeviceToHost));
@@ -521,6 +534,15 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
               double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status) {
   return fcst_dropin(ctx, B, N, p, H, Nd, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, elb, svz, z, seed,
                      sweep, fcstY, fcstYcensor, yhat, scores, status, false, 0.0, nullptr, nullptr);
+}
+
+int ccmm_fcst_big(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI,
+                  const double* invA, const double* logSV0, const double* sqrtPHI,
+                  const double* Xjumpoff, const double* yrealized, const uint8_t* ndxYields,
+                  double elb, const double* svz, const double* z, uint64_t seed, int sweep,
+                  double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status) {
+  return fcst_dropin(ctx, B, N, p, H, Nd, PAI, invA, logSV0, sqrtPHI, Xjumpoff, yrealized, ndxYields, elb, svz, z, seed,
+                     sweep, fcstY, fcstYcensor, yhat, scores, status, false, 0.0, nullptr, nullptr, true);
 }
 
 int ccmm_fcst_irf1(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI, const double* invA,

@@ -9,6 +9,8 @@
 namespace ccmm {
 
 constexpr int kFcstMaxN = 32;
+constexpr int kMvnMaxD = 12;         // series at the ELB the censored scores take (mvn_lattice_cdf, ccmm_fcst_dev.h)
+constexpr int kMvnPts = 64 * 1024;   // points of its lattice rule
 
 struct GLNodes {  // Gauss-Legendre half rules (negative nodes) for n = 6, 12, 20 (Genz BVN)
   double x[3][10];

@@ -92,7 +92,9 @@ def _drop_chain_axis(res, B):
 def _run_with_predictive_density(ch, m, burn, MCMCdraws, ndxYIELDS, ELBbound, yrealized,
                                  fcstNdraws, fcstNhorizons, doprogress):
     """Kept-draw loop of mcmcVAR.m:278-381 with the predictive density of each kept draw
-    simulated inside the chain set (ccmm_chains_set_fcst: no host round trip per draw),
+    simulated inside the chain set (ccmm_chains_set_fcst: no host round trip per draw; N <= 128, the
+    large-N kernels of ccmm_fcst_big.hip from N = 33 on -- linear, shadow-rate and block-hybrid samplers; the
+    hybrid sampler's predictive density and IRF1scale are refused by the library at N > 32),
     then the reshapes and means of :400-425.  Returns fcstYdraws, fcstYhat,
     fcstYcensorDraws, fcstYcensorHat, fcstYshadowDraws, fcstYshadowHat, fcstYhatRB,
     fcstLogscoreDraws, fcstLogscoreELBdraws, fcstLogscoreXdraws, fcstLogscoreIdraws (each

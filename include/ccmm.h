@@ -343,7 +343,10 @@ int ccmm_chains_pai_moments(ccmm_chains* ch, int reset, double* sum, double* sum
  * simulation on the K + Nyields p states with the actual rates max(shadow, ELB), :615-623)
  * and the one-step log scores (logscoreGaussian.m, logscoreGaussianCensored.m).
  * CRN mode appends randn(N, H*Nd) and randn(N, H, Nd) (block CCMM_RNG_FCST) to every
- * sweep's CRN record.  Linear and block-hybrid models, N <= 32.
+ * sweep's CRN record.  Linear, shadow-rate (linear forecast form) and block-hybrid models: N <= 128 (N <= 32:
+ * one wave per draw, ccmm_fcst.hip; 32 < N <= 128: the draws batched as MFMA columns, ccmm_fcst_big.hip; same
+ * records, same CRN and Philox layout).  Hybrid model: N <= 32 ("hybrid predictive density supports N <= 32").
+ * ccmm_chains_set_irf1 is refused at N > 32 ("doIRF1 supports N <= 32").
  *   ndxYields N bytes (ndxYIELDS), keep_paths != 0 keeps every path for quantiles/CRPS.
  * Call after set_elb_model (block hybrid) and before sweeping. */
 int ccmm_chains_set_fcst(ccmm_chains* ch, int H, int Nd, const uint8_t* ndxYields, int keep_paths);
@@ -798,6 +801,14 @@ int ccmm_fcst(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* P
               const double* Xjumpoff, const double* yrealized, const uint8_t* ndxYields,
               double elb, const double* svz, const double* z, uint64_t seed, int sweep,
               double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status);
+/* ccmm_fcst (N <= 32) on the kernels of the large-N path: 1 <= N <= 128, K = N*p + 1 <= 1536, same arguments,
+ * same outputs, the same normals in Philox mode; the sums of the companion recursion and of the scores run in
+ * another order, so the outputs agree with ccmm_fcst to rounding, not bit for bit. */
+int ccmm_fcst_big(ccmm_ctx* ctx, int B, int N, int p, int H, int Nd, const double* PAI,
+                  const double* invA, const double* logSV0, const double* sqrtPHI,
+                  const double* Xjumpoff, const double* yrealized, const uint8_t* ndxYields,
+                  double elb, const double* svz, const double* z, uint64_t seed, int sweep,
+                  double* fcstY, double* fcstYcensor, double* yhat, double* scores, int* status);
 /* ccmm_fcst with the doIRF1 simulations of mcmcVARshadowrate.m:588-605: the linear recursion (ltitr) twice more
  * on the draw's shocks, the structural shock of variable 1 (index 0) at horizon 1 replaced by +irf1scale and by
  * -irf1scale.  fcstY1plus, fcstY1minus N x H x Nd x B (fcstYdraws1plus / fcstYdraws1minus as simulated, laid out
