@@ -223,11 +223,35 @@ def _run_chain_set(ch, burn, MCMCdraws, doprogress, step=50):
             print(f"draws {done + n}/{MCMCdraws}" if store else f"burn-in {done + n}/{burn}")
 
 
+class _Summary(NamedTuple):
+    """One device summary (Chains.summaries) that a model's batch driver takes of a vintage's kept draws, under
+    the key ``src`` of _Field.  A model's rows are taken in their order."""
+    src: str
+    source: int              # 0 the uncensored paths, 1 the censored recursion's, 2 PAI
+    floor: str = ""          # rows floored at ELBbound first: y ndxYIELDS, s ndxSHADOWRATE
+    cum: bool = False        # the cumcode rows cumulated over the horizons, against the cumulated yrealized
+    rows: bool = False       # the yield rows only, without realized values
+    post: bool = False       # with postprocess only
+
+
+# goVARshadowrateBlockHybrid.m:349-480 (and goVARhybrid.m): ydraws are the censored paths
+_SUMMARIES_ELB = (_Summary("yd", 1), _Summary("yc", 1, cum=True), _Summary("sh", 0, rows=True), _Summary("pa", 2))
+# goVARshadowrate.m:356-495: ydraws = the uncensored paths with the yields floored, ycensordraws with the shadow
+# rates floored, shadowratedraws unfloored
+_SUMMARIES_SHADOWRATE = (_Summary("pa", 2), _Summary("yd", 0, floor="y"), _Summary("yz", 1, floor="s"),
+                         _Summary("yc", 0, floor="y", cum=True, post=True), _Summary("sh", 0, rows=True, post=True))
+# goVAR.m:297-340 on mcmcVAR.m:400-414: ydraws uncensored, ycensordraws as simulated (every yield floored inside
+# the recursion), yshadowdraws = ydraws with the yields floored afterwards
+_SUMMARIES_STANDARD = (_Summary("pa", 2), _Summary("yd", 0), _Summary("yz", 1), _Summary("ys", 0, floor="y"),
+                       _Summary("yc", 0, cum=True, post=True))
+
+
 @dataclass(frozen=True)
 class _Model:
-    """What differs between the ELB models.  Every driver reads these facts from _MODELS[name]; a model is one
-    row there, plus whatever it truly does differently."""
+    """What differs between the models of the batch driver.  Every driver reads these facts from _MODELS[name]; a
+    model is one row there, plus whatever it truly does differently."""
     abi: int                 # CCMM_MODEL_* of the chain set
+    summaries: tuple         # the _Summary rows of its driver
     ffr_lags: bool           # build_hybrid: K = N p + 1 + Ns p (lags of the actual rates); else build_bh
     actual_block: bool       # actualrateBlock goes to the device; else every equation is on one design
     ps_every_sweep: bool     # PS proposals from sweep 1; else from ceil(MCMCburnin / 2)
@@ -239,10 +263,21 @@ class _Model:
     native: bool             # ccmm_run_batch runs it
     maxlambda: bool          # its driver computes the maximum VAR roots
     stationarity: bool       # check_stationarity is honoured; else warned about and ignored
+    elb: bool = True         # it has an ELB block: shadow rates, the Gibbs / PS step, the ELB window and their
+    #                          results; else (mcmcVAR.m) the linear chain set, Ns = 0 and no ELB call at all
+
+    @property
+    def censor_report(self):
+        """Its driver reports the censored recursion beside the uncensored paths (fcstYhatRB, fcstYcensor*), and its
+        fcstYhat needs summaries of the kept paths: they stay in HBM whatever ``postprocess`` says."""
+        return self.linear_fcst or not self.elb
 
     def build(self, thisT, p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean, ELBbound,
               elbT0, doRATSprior, actualrateBlock=None):
-        """Host setup of one vintage (model.build_hybrid / model.build_bh)."""
+        """Host setup of one vintage (model.build_hybrid / model.build_bh; without an ELB block model.build_var
+        alone, as ``var`` of a namespace)."""
+        if not self.elb:
+            return SimpleNamespace(var=build_var(thisT, p, np_, data0, ydates0, minnesotaPriorMean, doRATSprior))
         if self.ffr_lags:
             return build_hybrid(thisT, p, np_, data0, ydates0, ndxSHADOWRATE, minnesotaPriorMean, ELBbound,
                                 elbT0, doRATSprior)
@@ -253,15 +288,19 @@ class _Model:
 
 
 _MODELS = {
-    "blockhybrid": _Model(abi=_abi.MODEL_BLOCKHYBRID, ffr_lags=False, actual_block=True, ps_every_sweep=False,
-                          ps_missingrate=False, linear_fcst=False, Nproposals=1000, native=True, maxlambda=True,
-                          stationarity=True),
-    "hybrid": _Model(abi=_abi.MODEL_HYBRID, ffr_lags=True, actual_block=False, ps_every_sweep=True,
-                     ps_missingrate=True, linear_fcst=False, Nproposals=1000, native=True, maxlambda=False,
-                     stationarity=False),
-    "shadowrate": _Model(abi=_abi.MODEL_SHADOWRATE, ffr_lags=False, actual_block=False, ps_every_sweep=False,
-                         ps_missingrate=True, linear_fcst=True, Nproposals=100, native=False, maxlambda=True,
-                         stationarity=True),
+    "blockhybrid": _Model(abi=_abi.MODEL_BLOCKHYBRID, summaries=_SUMMARIES_ELB, ffr_lags=False, actual_block=True,
+                          ps_every_sweep=False, ps_missingrate=False, linear_fcst=False, Nproposals=1000, native=True,
+                          maxlambda=True, stationarity=True),
+    "hybrid": _Model(abi=_abi.MODEL_HYBRID, summaries=_SUMMARIES_ELB, ffr_lags=True, actual_block=False,
+                     ps_every_sweep=True, ps_missingrate=True, linear_fcst=False, Nproposals=1000, native=True,
+                     maxlambda=False, stationarity=False),
+    "shadowrate": _Model(abi=_abi.MODEL_SHADOWRATE, summaries=_SUMMARIES_SHADOWRATE, ffr_lags=False,
+                         actual_block=False, ps_every_sweep=False, ps_missingrate=True, linear_fcst=True,
+                         Nproposals=100, native=False, maxlambda=True, stationarity=True),
+    # goVAR.m, modellabel standardVAR: mcmcVAR per vintage.  ("linear" stays no model of the batch driver.)
+    "standard": _Model(abi=_abi.MODEL_LINEAR, summaries=_SUMMARIES_STANDARD, ffr_lags=False, actual_block=False,
+                       ps_every_sweep=False, ps_missingrate=False, linear_fcst=False, Nproposals=0, native=False,
+                       maxlambda=True, stationarity=True, elb=False),
 }
 
 
@@ -617,6 +656,7 @@ def goVAR_batch(data0, ydates0, Tjumpoffs, p, np_, MCMCdraws, fcstNdraws, fcstNh
     (goVAR.m:262-267; ``realized_values``).  ``run_vintage(thisT, yrealized, seed)``
     replaces the mcmcVAR call (tests use it to drive the sharding on CPU).  ``device``
     defaults to the rank's LOCAL_RANK under a process group.  Returns a dict on every rank.
+    goVARstandard_batch runs the same vintages as one device-resident chain set with goVAR.m's full result set.
 
     Compute_diagnostics=True (goVAR.m's switch, Diagnostics.m) adds diagSVpsrf (N x V), diagSVif (N x 3 x V),
     diagPAIpsrf / diagInvApsrf / diagPHIpsrf (V) and diagPAIif / diagInvAif / diagPHIif (3 x V): the block means of
@@ -725,16 +765,26 @@ def VMA(PAI_all, N, p, H, *, device=None):
 
 
 def save_qrt_mat(filename, res, *, data, ydates, p, ncode, tcode, cumcode, ndxSHADOWRATE,
-                 ndxOTHERYIELDS, ELBbound, actualrateBlock, datalabel, modellabel, MCMCdraws,
-                 fcstNhorizons, doQuarterly=False):
+                 ndxOTHERYIELDS, ELBbound, actualrateBlock=None, datalabel, modellabel, MCMCdraws,
+                 fcstNhorizons, doQuarterly=False, varlist="shadowrate"):
     """The QRT summary file of goVARshadowrateBlockHybrid.m:641-669 (varlist: data, ydates, p,
     Tjumpoffs, N, ncode, tcode, cumcode, fcst*, fcstNhorizons, PAI*, shadowrate*, missingrate*, VMA*, sumFFR*,
     ndx*, ELBbound, ELBdummy, actualrateBlock, datalabel, modellabel, doQuarterly,
     setQuantiles, MCMCdraws) from a goVARshadowrateBlockHybrid_batch result.  MATLAB
     -v7.3 is HDF5; this writes the same names and shapes as a v5 MAT-file (scipy.io.savemat).
     Index variables are 1-based as in MATLAB; missingrate* are NaN (doELBsampleAlternate is
-    false in the driver)."""
+    false in the driver).
+
+    varlist="standard" writes the list of goVAR.m:552-566 from a goVARstandard_batch result instead: the same
+    without ELBdummy, actualrateBlock (not needed then), shadowrate* and missingrate*; sumFFR* and VMA* where the
+    result has them."""
     from scipy.io import savemat
+    if varlist not in ("shadowrate", "standard"):
+        raise ValueError(f"varlist must be 'shadowrate' or 'standard', not {varlist!r}")
+    standard = varlist == "standard"
+    if actualrateBlock is None and not standard:
+        raise ValueError("save_qrt_mat: the shadow-rate drivers' file holds actualrateBlock; pass it, or "
+                         "varlist='standard' for goVAR.m's list")
     data = np.asarray(data, float)
     ndxS1 = np.asarray(ndxSHADOWRATE, int) + 1
     ndxO1 = np.asarray(ndxOTHERYIELDS, int) + 1
@@ -748,14 +798,18 @@ def save_qrt_mat(filename, res, *, data, ydates, p, ncode, tcode, cumcode, ndxSH
              ndxSHADOWRATE=ndxS1.astype(float)[None, :], ndxOTHERYIELDS=ndxO1.astype(float)[None, :],
              ndxYIELDS=np.union1d(ndxS1, ndxO1).astype(float)[None, :], ELBbound=float(ELBbound),
              ELBdummy=data[:, ndxS1 - 1] <= ELBbound,
-             actualrateBlock=np.asarray(actualrateBlock, bool)[None, :], datalabel=datalabel,
+             actualrateBlock=None if standard else np.asarray(actualrateBlock, bool)[None, :], datalabel=datalabel,
              modellabel=modellabel, doQuarterly=bool(doQuarterly), MCMCdraws=float(MCMCdraws),
              setQuantiles=np.asarray(res.get("setQuantiles", SET_QUANTILES), float)[None, :],
              missingrateVintagesMid=np.full((Tdata, Ns, V), np.nan),
              missingrateVintagesTails=np.full((Tdata, Ns, 4, V), np.nan))
+    if standard:                                       # goVAR.m:552-566 names none of these
+        for k in ("ELBdummy", "actualrateBlock", "missingrateVintagesMid", "missingrateVintagesTails"):
+            del m[k]
+    wild = ("fcst", "PAI", "VMA", "sumFFR") + (() if standard else ("shadowrate",))
     for k, v in res.items():
         # the reference's wildcards; shadowratePSRFchains (psrf across chains) is not a reference output
-        if k.startswith(("fcst", "PAI", "shadowrate", "VMA", "sumFFR")) and k != "shadowratePSRFchains" and isinstance(v, np.ndarray):
+        if k.startswith(wild) and k != "shadowratePSRFchains" and isinstance(v, np.ndarray):
             m[k] = v[None, :] if v.ndim == 1 else v
     savemat(filename, m, do_compression=True)
     return sorted(m)
@@ -777,7 +831,8 @@ def _bh_units(data0, ydates0, Tjumpoffs, p, np_, ndxSHADOWRATE, ndxOTHERYIELDS,
               minnesotaPriorMean, ELBbound, elbT0, doRATSprior, fcstNhorizons, model="blockhybrid"):
     """Host setup of every vintage (mcmcVARshadowrateBlockHybrid.m:30-295; model="hybrid":
     mcmcVARhybridGibbs.m:33-339; model="shadowrate": mcmcVARshadowrate.m, every equation on the
-    shadow-rate design) and its yrealized (goVARshadowrateBlockHybrid.m:267-283)."""
+    shadow-rate design; model="standard": mcmcVAR.m:28-187, where elbT0 is not read) and its yrealized
+    (goVARshadowrateBlockHybrid.m:267-283 == goVAR.m:252-267; an empty ndxSHADOWRATE floors nothing)."""
     out = []
     for thisT in Tjumpoffs:
         bm = _MODELS[model].build(int(thisT), p, np_, data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS,
@@ -791,20 +846,23 @@ def _bh_chain_set(ctx, units, C, *, seed, ids, store_capacity, gibbsburn, ELBbou
                   fcstNhorizons=None, Nd=None, keep_paths=False, model="blockhybrid"):
     """One device-resident chain set holding every unit (vintage) as a data slot with C
     chains each (the parfor over vintages as one batch), reference initialisation per
-    chain (:308-317), predictive density on every stored sweep."""
+    chain (:308-317), predictive density on every stored sweep.  A model without an ELB block is the linear
+    chain set of mcmcVAR (Ns = 0, elbTmax = 0, no ELB call; mcmcVAR.m:360-366 floors every yield inside the
+    censored recursion, which is set_fcst's default)."""
     bm0 = units[0][1]
     N, p = bm0.var.N, bm0.var.p
     Tmax = max(u[1].var.T for u in units)
-    elbTmax = max(max(u[1].elbT for u in units), 1)
     B = C * len(units)
     spec = _MODELS[model]
+    elbTmax = max(max(u[1].elbT for u in units), 1) if spec.elb else 0
     ch = _abi.Chains(ctx, N=N, p=p, T=Tmax, B=B, ndata=len(units), crn=False,
                      store_capacity=store_capacity, seed=int(seed), model=spec.abi,
-                     Ns=len(bm0.ndxS), elbTmax=elbTmax, elb_gibbsburn=gibbsburn, elb=ELBbound)
+                     Ns=len(bm0.ndxS) if spec.elb else 0, elbTmax=elbTmax, elb_gibbsburn=gibbsburn, elb=ELBbound)
     for s, (_, bm, _) in enumerate(units):
         m = bm.var
         ch.set_data(s, m.Y, m.X, m.iVdiag, m.iVb, m.sPHI, m.Vol_0mean, m.Vol_0vcvsqrt)
-    ch.set_elb_model(bm0.ndxS, bm0.actual_block if spec.actual_block else None)
+    if spec.elb:
+        ch.set_elb_model(bm0.ndxS, bm0.actual_block if spec.actual_block else None)
     yields = _mask(N, ndxYIELDS)
     if fcstNhorizons:
         ch.set_fcst(fcstNhorizons, Nd, yields, keep_paths=keep_paths)
@@ -819,7 +877,8 @@ def _bh_chain_set(ctx, units, C, *, seed, ids, store_capacity, gibbsburn, ELBbou
                 sqrtht=np.ones((Tmax, N, B), order="F"), h=np.zeros((Tmax, N, B), order="F"),
                 sqrtPHI=np.zeros((N, N, B), order="F"))
     for s, (_, bm, yr) in enumerate(units):
-        ch.set_elb_slot(s, bm.elbT0, bm.sNaN)
+        if spec.elb:
+            ch.set_elb_slot(s, bm.elbT0, bm.sNaN)
         if fcstNhorizons:
             ch.set_fcst_slot(s, yr[:, 0])
         st = initial_state(bm.var, C)
@@ -840,8 +899,9 @@ def _bh_switches(ch, spec, burn, *, Nproposals, elb_ps=True, missing=False, alte
     the treatment of the ELB months (missing: doELBsampling = false, every sweep's unconstrained draw is the
     data; alternate: one more such draw per sweep), the PS proposals from the model's first PS sweep
     (elb_ps=False, Nproposals=0 or missing: none) with proposal 1 kept as missingrate if asked, and the
-    stationarity redraws.  Returns whether any sweep proposes."""
-    use_ps = bool(elb_ps and Nproposals and not missing)
+    stationarity redraws (all that applies to a model without an ELB block).  Returns whether any sweep
+    proposes."""
+    use_ps = bool(spec.elb and elb_ps and Nproposals and not missing)
     if missing or alternate:
         ch.set_elb_treatment(missing=missing, alternate=alternate)
     if use_ps:
@@ -857,59 +917,77 @@ class _Field(NamedTuple):
     """One per-vintage array of the batch drivers' result: ``out[name]`` has ``shape`` plus a last axis over the
     vintages, NaN (``fill``) where a vintage failed."""
     name: str
-    src: str            # a device summary (Chains.summaries) of the vintage's kept draws: pa PAI, yd ydraws, yc
-    #                     ycumdraws, yz ycensordraws (shadow-rate VAR), sh shadowratedraws; or scores / logscore
-    #                     (the one-step score draws, their log mean exp), ycr (cumulated yrealized), host; vm:
-    #                     Chains.vma_summaries of the vintage's stored draws
+    src: str            # a device summary (Chains.summaries, the model's _Summary rows) of the vintage's kept draws:
+    #                     pa PAI, yd ydraws, yc ycumdraws, yz ycensordraws, ys yshadowdraws (standard VAR), sh
+    #                     shadowratedraws; or scores / logscore (the one-step score draws, their log mean exp), ycr
+    #                     (cumulated yrealized), host; vm: Chains.vma_summaries of the vintage's stored draws
     stat: object        # of a summary: mean, stdev, median, quantiles, crps; of the scores: their column
     shape: tuple        # in terms of K, N, H, Ny, nq, Ns, nd = fcstNdraws C, nr = MCMCdraws C
-    need: str = ""      # p: with postprocess; f: model with linear_fcst; l: with maxlambda; v: doLoMem=False;
-    #                     s: with a policy-rate variable for sumFFR
+    need: str = ""      # p: with postprocess; e: model with an ELB block, u: without one (the standard VAR, whose
+    #                     ydraws are the uncensored paths); c: model that reports the censored recursion
+    #                     (_Model.censor_report); l: with maxlambda; v: doLoMem=False; s: with a policy-rate
+    #                     variable for sumFFR
     fill: float = np.nan
 
 
 _FIELDS = (
-    _Field("fcstYmvlogscore", "logscore", 1, ()), _Field("fcstYmvlogscoreX", "logscore", 2, ()),
+    # the score columns of get_fcst: 0 uncensored, 1 censored at the ELB, 2 and 3 the X and I subsets; the ELB
+    # models' drivers report column 1 as fcstYmvlogscore, goVAR.m:398-412 reports all four
+    _Field("fcstYmvlogscore", "logscore", 1, (), "e"), _Field("fcstYmvlogscore", "logscore", 0, (), "u"),
+    _Field("fcstYmvlogscoreELB", "logscore", 1, (), "u"), _Field("fcstYmvlogscoreX", "logscore", 2, ()),
     _Field("fcstYmvlogscoreI", "logscore", 3, ()),
-    _Field("fcstYhat", "host", None, ("N", "H")), _Field("fcstShadowYhat", "host", None, ("Ny", "H")),
+    _Field("fcstYhat", "host", None, ("N", "H"), "e"), _Field("fcstYhat", "yd", "mean", ("N", "H"), "u"),
+    _Field("fcstShadowYhat", "host", None, ("Ny", "H"), "e"),
     _Field("fcstYrealized", "host", None, ("N", "H")),
     _Field("PAImean", "pa", "mean", ("K", "N")), _Field("PAIstdev", "pa", "stdev", ("K", "N")),
-    _Field("countELBaccept", "host", None, (), fill=-1),
-    _Field("shadowratePSRF", "host", None, ("Ns",)),                     # :213
-    _Field("shadowratePSRFchains", "host", None, ("Ns",)),               # psrf across chains (no ref.)
-    _Field("fcstYhatRB", "host", None, ("N", "H"), "f"), _Field("fcstYcensorhat", "yz", "mean", ("N", "H"), "f"),
+    _Field("countELBaccept", "host", None, (), "e", fill=-1),
+    _Field("shadowratePSRF", "host", None, ("Ns",), "e"),                # :213
+    _Field("shadowratePSRFchains", "host", None, ("Ns",), "e"),          # psrf across chains (no ref.)
+    _Field("fcstYhatRB", "host", None, ("N", "H"), "c"), _Field("fcstYcensorhat", "yz", "mean", ("N", "H"), "c"),
+    _Field("fcstYshadowhat", "ys", "mean", ("N", "H"), "u"),             # goVAR.m:187-192, all N rows
     _Field("fcstYmedian", "yd", "median", ("N", "H"), "p"), _Field("fcstYcrps", "yd", "crps", ("N", "H"), "p"),
     _Field("fcstYquantiles", "yd", "quantiles", ("N", "H", "nq"), "p"),
     _Field("fcstYcumrealized", "ycr", None, ("N", "H"), "p"), _Field("fcstYcumhat", "host", None, ("N", "H"), "p"),
     _Field("fcstYcummedian", "yc", "median", ("N", "H"), "p"), _Field("fcstYcumcrps", "yc", "crps", ("N", "H"), "p"),
     _Field("fcstYcumquantiles", "yc", "quantiles", ("N", "H", "nq"), "p"),
-    _Field("fcstShadowYmedian", "sh", "median", ("Ny", "H"), "p"),
-    _Field("fcstShadowYquantiles", "sh", "quantiles", ("Ny", "H", "nq"), "p"),
+    _Field("fcstShadowYmedian", "sh", "median", ("Ny", "H"), "pe"),
+    _Field("fcstShadowYquantiles", "sh", "quantiles", ("Ny", "H", "nq"), "pe"),
     _Field("PAImedian", "pa", "median", ("K", "N"), "p"), _Field("PAIquantiles", "pa", "quantiles", ("K", "N", "nq"), "p"),
-    _Field("fcstYmvlogscoreDraws", "scores", 1, ("nd",), "p"), _Field("fcstYmvlogscoreXdraws", "scores", 2, ("nd",), "p"),
-    _Field("fcstYmvlogscoreIdraws", "scores", 3, ("nd",), "p"),
-    _Field("fcstYcensormedian", "yz", "median", ("N", "H"), "pf"), _Field("fcstYcensorcrps", "yz", "crps", ("N", "H"), "pf"),
-    _Field("fcstYcensorquantiles", "yz", "quantiles", ("N", "H", "nq"), "pf"),
+    _Field("fcstYmvlogscoreDraws", "scores", 1, ("nd",), "pe"), _Field("fcstYmvlogscoreDraws", "scores", 0, ("nd",), "pu"),
+    _Field("fcstYmvlogscoreELBdraws", "scores", 1, ("nd",), "pu"),
+    _Field("fcstYmvlogscoreXdraws", "scores", 2, ("nd",), "p"), _Field("fcstYmvlogscoreIdraws", "scores", 3, ("nd",), "p"),
+    _Field("fcstYcensormedian", "yz", "median", ("N", "H"), "pc"), _Field("fcstYcensorcrps", "yz", "crps", ("N", "H"), "pc"),
+    _Field("fcstYcensorquantiles", "yz", "quantiles", ("N", "H", "nq"), "pc"),
+    _Field("fcstYshadowmedian", "ys", "median", ("N", "H"), "pu"), _Field("fcstYshadowcrps", "ys", "crps", ("N", "H"), "pu"),
+    _Field("fcstYshadowquantiles", "ys", "quantiles", ("N", "H", "nq"), "pu"),
     _Field("drawsMaxVARroot", "host", None, ("nr",), "l"),
     _Field("VMAmid", "vm", "median", ("N", "N", "H"), "v"), _Field("VMAtail", "vm", "quantiles", ("N", "N", "H", "nq"), "v"),
     _Field("sumFFRmid", "vm", "sumMedian", ("N",), "vs"), _Field("sumFFRtail", "vm", "sumQuantiles", ("N", "nq"), "vs"),
 )
 
 # forecast errors taken at the end of the run where both terms are there: name, realized, forecast
-# (goVARshadowrateBlockHybrid.m:453-454, 463-464; goVARshadowrate.m:487-488)
+# (goVARshadowrateBlockHybrid.m:453-454, 463-464; goVARshadowrate.m:487-488; goVAR.m:418-447)
 _ERROR_FIELDS = (("fcstYhaterror", "fcstYrealized", "fcstYhat"),
                  ("fcstYcensorhaterror", "fcstYrealized", "fcstYcensorhat"),
                  ("fcstYcensormederror", "fcstYrealized", "fcstYcensormedian"),
+                 ("fcstYshadowhaterror", "fcstYrealized", "fcstYshadowhat"),
+                 ("fcstYshadowmederror", "fcstYrealized", "fcstYshadowmedian"),
                  ("fcstYmederror", "fcstYrealized", "fcstYmedian"),
                  ("fcstYcumhaterror", "fcstYcumrealized", "fcstYcumhat"),
                  ("fcstYcummederror", "fcstYcumrealized", "fcstYcummedian"))
 
 
-def _fields(postprocess, linear_fcst, maxlambda, vma=False, sumffr=False):
-    """The rows of _FIELDS that a run with these switches fills."""
-    have = ("p" if postprocess else "") + ("f" if linear_fcst else "") + ("l" if maxlambda else "") + \
-        ("v" if vma else "") + ("s" if sumffr else "")
+def _fields(postprocess, linear_fcst, maxlambda, vma=False, sumffr=False, elb=True):
+    """The rows of _FIELDS that a run with these switches fills; linear_fcst and elb are the model's
+    (_Model.linear_fcst, _Model.elb)."""
+    have = ("p" if postprocess else "") + ("e" if elb else "u") + ("c" if linear_fcst or not elb else "") + \
+        ("l" if maxlambda else "") + ("v" if vma else "") + ("s" if sumffr else "")
     return [f for f in _FIELDS if set(f.need) <= set(have)]
+
+
+def _run_fields(b):
+    """_fields of the run ``b``."""
+    return _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda, b.vma, b.ffr is not None, b.spec.elb)
 
 
 def _diag_fields(N):
@@ -1000,28 +1078,27 @@ def _drain_held(ch, b, acc, nv, use_ps):
 
 def _vintage_summaries(ch, b, k, yr, yields):
     """goVARshadowrateBlockHybrid.m:349-480 on the device for the vintage in data slot k: the summaries of
-    _FIELDS' sources, keyed by them, plus ycr (yrealized cumulated for ``cumcode``)."""
-    pct, cumcode = b.pct, b.cumcode
+    _FIELDS' sources, keyed by them (the model's _Summary rows), plus ycr (yrealized cumulated for ``cumcode``).
+    Without postprocess only the means are wanted: no percentiles, no CRPS."""
+    post, cumcode = b.postprocess, b.cumcode
     ycr = np.array(yr, float)
     if cumcode is not None:
         ycr[cumcode] = np.cumsum(ycr[cumcode], axis=1)              # :353
-    if not b.spec.linear_fcst:
-        yd = ch.summaries(1, k, realized=yr, pct=pct)                   # ydraws
-        yc = ch.summaries(1, k, cumcode=cumcode, realized=ycr, pct=pct)  # ycumdraws
-        sh = ch.summaries(0, k, rows=yields, pct=pct)                   # shadowratedraws
-        pa = ch.summaries(2, k, pct=pct)                                # PAI_all
-        return dict(yd=yd, yc=yc, sh=sh, pa=pa, ycr=ycr)
-    # goVARshadowrate.m:356-495: ydraws = uncensored paths, yields floored; the
-    # censored paths with the shadow rates floored; shadowratedraws unfloored
-    post = b.postprocess
-    q = dict(ycr=ycr, pa=ch.summaries(2, k, pct=pct if post else ()))
-    q["yd"] = ch.summaries(0, k, realized=yr if post else None, pct=pct if post else (), floor_rows=yields,
-                           floor=b.ELBbound)
-    q["yz"] = ch.summaries(1, k, realized=yr if post else None, pct=pct if post else (), floor_rows=b.smask,
-                           floor=b.ELBbound)
-    if post:
-        q["yc"] = ch.summaries(0, k, cumcode=cumcode, realized=ycr, pct=pct, floor_rows=yields, floor=b.ELBbound)
-        q["sh"] = ch.summaries(0, k, rows=yields, pct=pct)
+    q = dict(ycr=ycr)
+    floors = dict(y=yields, s=b.smask)
+    for s in b.spec.summaries:
+        if s.post and not post:
+            continue
+        kw = dict(pct=b.pct if post else ())
+        if s.rows:
+            kw["rows"] = yields
+        elif s.source != 2 and post:
+            kw["realized"] = ycr if s.cum else yr
+        if s.cum:
+            kw["cumcode"] = cumcode
+        if s.floor:
+            kw.update(floor_rows=floors[s.floor], floor=b.ELBbound)
+        q[s.src] = ch.summaries(s.source, k, **kw)
     return q
 
 
@@ -1034,24 +1111,23 @@ def _vintage_result(b, acc, k, unit, q, diag, vm=None):
     cs = slice(k * C, (k + 1) * C)
     nk = b.MCMCdraws * C
     scores, shadow, miss = acc.scores, acc.shadow, acc.miss
-    r = dict(thisT=thisT, fcstYrealized=yr, countELBaccept=None if acc.nacc is None else int(acc.nacc[cs].sum()),
-             fcstYhat=acc.fYcsum[:, :, cs].sum(axis=2) / (nk * b.Nd),
-             fcstShadowYhat=acc.fYsum[ndxY][:, :, cs].sum(axis=2) / (nk * b.Nd))
+    r = dict(thisT=thisT, fcstYrealized=yr)
+    if b.spec.elb:
+        r.update(countELBaccept=None if acc.nacc is None else int(acc.nacc[cs].sum()),
+                 fcstYhat=acc.fYcsum[:, :, cs].sum(axis=2) / (nk * b.Nd),
+                 fcstShadowYhat=acc.fYsum[ndxY][:, :, cs].sum(axis=2) / (nk * b.Nd))
+    if b.spec.censor_report:
+        r["fcstYhatRB"] = acc.yhsum[:, :, cs].sum(axis=2) / nk             # mcmcVARshadowrate.m:639, mcmcVAR.m:400
     if b.spec.linear_fcst:
-        RB = acc.yhsum[:, :, cs].sum(axis=2) / nk                          # mcmcVARshadowrate.m:639
+        RB = r["fcstYhatRB"]
         yh = RB.copy()
         yh[ndxY] = q["yd"]["mean"].reshape(N, H, order="F")[ndxY]          # :683-684
-        r.update(fcstYhat=yh, fcstYhatRB=RB, fcstShadowYhat=RB[ndxY])
+        r.update(fcstYhat=yh, fcstShadowYhat=RB[ndxY])
     if q is None:
         r["PAImean"] = acc.Psum[:, :, cs].sum(axis=2) / nk
         var = acc.P2sum[:, :, cs].sum(axis=2) / nk - r["PAImean"] ** 2
         r["PAIstdev"] = np.sqrt(np.maximum(var, 0.0))               # std(.,1,1): 1/n
-    elif b.postprocess:
-        yh = r["fcstYhat"].copy()
-        if b.cumcode is not None:
-            yh[b.cumcode] = np.cumsum(yh[b.cumcode], axis=1)                # :355
-        r["fcstYcumhat"] = yh
-    for f in _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda, b.vma, b.ffr is not None):
+    for f in _run_fields(b):
         if f.src == "vm":
             r[f.name] = vm[f.stat]
         elif f.src == "logscore":
@@ -1061,6 +1137,11 @@ def _vintage_result(b, acc, k, unit, q, diag, vm=None):
         elif q is not None and f.src in q:
             r[f.name] = q[f.src] if f.stat is None else \
                 q[f.src][f.stat].reshape([b.dims[d] for d in f.shape], order="F")
+    if q is not None and b.postprocess:
+        yh = r["fcstYhat"].copy()
+        if b.cumcode is not None:
+            yh[b.cumcode] = np.cumsum(yh[b.cumcode], axis=1)                # :355, goVAR.m:303
+        r["fcstYcumhat"] = yh
     if miss is not None and bm.elbT > 0:
         # missingrate_all permuted to (Nobs, Ns, draws): MATLAB median (NaN if any draw
         # is NaN) and prctile (NaN draws removed), goVARshadowrate.m:345-348
@@ -1148,14 +1229,14 @@ def _batch_out(b, allv, Tjumpoffs, assignment, Tdata, jumpoff):
     with the vintage last, by _FIELDS, then the forecast errors."""
     V, Ns = len(Tjumpoffs), b.Ns
     out = dict(Tjumpoffs=np.array(Tjumpoffs), assignment=assignment)
-    fields = _fields(b.postprocess, b.spec.linear_fcst, b.maxlambda, b.vma, b.ffr is not None)
+    fields = _run_fields(b)
     for f in fields:
         out[f.name] = np.full(tuple(b.dims[d] for d in f.shape) + (V,), f.fill)
-    windows = ("shadowrate",) + (("missingrate",) if b.spec.linear_fcst or b.missing else ())
+    windows = (("shadowrate",) + (("missingrate",) if b.spec.linear_fcst or b.missing else ())) if b.spec.elb else ()
     for w in windows:                                  # months x Ns: median, prctile [5 25 75 95]
         out[w + "VintagesMid"] = np.full((Tdata, Ns, V), np.nan)
         out[w + "VintagesTails"] = np.full((Tdata, Ns, 4, V), np.nan)
-    kept = ("PAI_all", "shadowrate_all") if b.keep_draws else ()
+    kept = (("PAI_all",) + (("shadowrate_all",) if b.spec.elb else ())) if b.keep_draws else ()
     for nm in kept:
         out[nm] = {}
     diags = _diag_fields(b.N) if b.diagnostics else ()
@@ -1251,6 +1332,18 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     on the device (ccmm_chains_summaries_floor).  The forecast paths of every vintage stay in HBM
     until the summaries are taken (Python engine only).
 
+    model="standard" runs goVAR.m (goVARstandard_batch): mcmcVAR per vintage on the linear chain set, without any
+    ELB step.  Its results are goVAR.m:145-219: fcstYhat the mean of the uncensored paths (mcmcVAR.m:404),
+    fcstYhatRB the zero-shock mean path, fcstYcensor* the censored recursion (every yield floored inside it,
+    mcmcVAR.m:360-366), fcstYshadow* (N x H, all rows) the uncensored paths with the yields floored afterwards
+    (:406-411), the four log scores fcstYmvlogscore{,ELB,X,I} (fcstYmvlogscore is the uncensored one here), PAI*
+    and drawsMaxVARroot; postprocess=True adds the medians, errors, CRPS and quantiles of the four path sets
+    (fcstY*, fcstYcum*, fcstYcensor*, fcstYshadow*) and the four score draws.  No shadowrate*, missingrate*,
+    fcstShadowY*, countELBaccept or PSRF key is returned.  Python engine only, and doELBsampling=False is
+    refused.  The kept paths of every vintage of a rank stay in HBM until its summaries are taken, whatever
+    ``postprocess`` says: 2 N H fcstNdraws nchains 8 bytes per vintage, 154 MB at the reference size (N = 20,
+    H = 48, fcstNdraws = 10 000, one chain), about 25 GB for its 164 vintages on one device.
+
     keep_draws=True also returns the kept draws per vintage: PAI_all[v] (M x K x N x C) and
     shadowrate_all[v] (M x Ns x elbT x C).  shadowratePSRF (Ns x V) is DiagnosticsShadowrate of each
     vintage's kept shadow rates over the months at the ELB (:322-325, ccmm_shadowrate_psrf: the
@@ -1301,6 +1394,12 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     if missing and engine == "native":
         raise ValueError("doELBsampling=False runs on the Python engine (engine='python'): "
                          "ccmm_batch_config carries no treatment field")
+    spec = _MODELS.get(model)
+    if spec is None:
+        raise ValueError(f"unknown model {model!r}")
+    if missing and not spec.elb:
+        raise ValueError(f"doELBsampling=False: model={model!r} has no ELB step whose months could be treated as "
+                         "missing data")
     data0 = np.asarray(data0, float)
     ydates0 = np.asarray(ydates0, float)
     Tdata, N = data0.shape
@@ -1317,15 +1416,12 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     burn = MCMCdraws if burnin is None else int(burnin)
     C = int(nchains)
     H = int(fcstNhorizons)
-    # ELB window start, global over vintages (:131-134)
-    elbT0 = elbT0_of(data0, ndxSHADOWRATE, ELBbound, p)
-    startELB = elbT0 + 1 + p                                            # 1-based month
+    # ELB window start, global over vintages (:131-134); a model without an ELB block has no window
+    elbT0 = elbT0_of(data0, ndxSHADOWRATE, ELBbound, p) if spec.elb else None
+    startELB = elbT0 + 1 + p if spec.elb else None                      # 1-based month
     rank = dist.get_rank() if dist is not None else 0
     size = dist.get_world_size() if dist is not None else 1
     device = _rank_device(dist, device)
-    spec = _MODELS.get(model)
-    if spec is None:
-        raise ValueError(f"unknown model {model!r}")
     if engine == "native" and not spec.native:
         raise ValueError(f"model={model!r} runs on the Python engine (ccmm_chains_summaries_floor)")
     if maxlambda and not spec.maxlambda:
@@ -1354,8 +1450,11 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
                              "ndxSHADOWRATE stops with an assignment error, so sumFFR has no defined variable; "
                              "name it with sumFFRndx=<one 0-based index>")
     K = N * p + 1 + (Ns * p if spec.ffr_lags else 0)
-    costs = [dm.unit_cost(t - p, K, N, n_cens=dm.censored_months(data0, ndxSHADOWRATE, ELBbound, startELB, t)) * C
-             for t in Tjumpoffs]
+    if spec.elb:
+        costs = [dm.unit_cost(t - p, K, N, n_cens=dm.censored_months(data0, ndxSHADOWRATE, ELBbound, startELB, t)) * C
+                 for t in Tjumpoffs]
+    else:
+        costs = [dm.unit_cost(t - p, K, N) * C for t in Tjumpoffs]
     assignment = dm.lpt_assign(costs, size)
     mine = assignment[rank]
     t0 = time.perf_counter()
@@ -1365,10 +1464,11 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
     t_setup = time.perf_counter() - t0
     ctx = context(device)
     pct = np.asarray(SET_QUANTILES if setQuantiles is None else setQuantiles, float)
-    # postprocess (and the shadow-rate VAR, whose yhat needs the floored draws): every kept draw and forecast
-    # path stays on the device until the per-vintage summaries (ccmm_chains_summaries) have been taken; with
-    # them, Compute_diagnostics or doLoMem=False the store holds every kept draw until the end of the attempt
-    dev = bool(postprocess or spec.linear_fcst)
+    # postprocess (and the shadow-rate and the standard VAR, whose yhat / yshadowhat need the floored draws): every
+    # kept draw and forecast path stays on the device until the per-vintage summaries (ccmm_chains_summaries) have
+    # been taken; with them, Compute_diagnostics or doLoMem=False the store holds every kept draw until the end of
+    # the attempt
+    dev = bool(postprocess or spec.censor_report)
     b = SimpleNamespace(                                 # what the steps of a run share; fixed over the attempts
         model=model, spec=spec, ctx=ctx, units=units, mine=mine, rank=rank, progress=progress,
         C=C, N=N, K=K, Ns=Ns, H=H, p=p, Nd=fcstNdraws // MCMCdraws, MCMCdraws=MCMCdraws, burn=burn,
@@ -1412,7 +1512,7 @@ def goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIEL
         dist.all_gather_object(objs, local)
         for d_ in objs:
             allv.update(d_)
-    out = _batch_out(b, allv, Tjumpoffs, assignment, Tdata, jumpoff=p + elbT0)   # :497
+    out = _batch_out(b, allv, Tjumpoffs, assignment, Tdata, jumpoff=p + elbT0 if spec.elb else None)   # :497
     n_units = len(mine) * C
     out["stats"] = dict(rank=rank, world=size, device=device, vintages_local=len(mine),
                         units_local=n_units, sweeps_local=n_units * (burn + MCMCdraws),
@@ -1496,6 +1596,20 @@ def goVARhybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPr
     same arguments and outputs as goVARshadowrateBlockHybrid_batch (PAI* over K = N p + 1 + Ns p)."""
     return goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean,
                                             model="hybrid", **kw)
+
+
+def goVARstandard_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean, *, maxlambda=True,
+                        **kw):
+    """goVAR.m (the quasi-real-time OOS run of the standard linear VAR, mcmcVAR per vintage, parfor at :242,
+    modellabel standardVAR) as one device-resident chain set per rank, with goVAR.m's full result set: see
+    model="standard" of goVARshadowrateBlockHybrid_batch, whose arguments it takes.  The maximum VAR roots are
+    always computed there (:343-353), so maxlambda defaults to True.  ndxSHADOWRATE (may be empty) only says
+    which realized values are floored at the ELB and which variable sumFFR* sums; the censored forecasts floor
+    ndxYIELDS = ndxSHADOWRATE and ndxOTHERYIELDS.  gibbsburn, Nproposals and elb_ps are accepted and ignored;
+    engine="native" and doELBsampling=False are refused.  Vintage v, chain c draws from Philox stream v nchains + c
+    of seed rndStream, so vintage 0 repeats mcmcVAR(thisT, ..., rndStream=seed, nchains=nchains)."""
+    return goVARshadowrateBlockHybrid_batch(data0, ydates0, ndxSHADOWRATE, ndxOTHERYIELDS, minnesotaPriorMean,
+                                            model="standard", maxlambda=maxlambda, **kw)
 
 
 # ---------------------------------------------------------------------------------------

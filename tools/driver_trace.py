@@ -7,7 +7,8 @@ applied; shape, dtype and sha256 of array bytes, repr of scalars).  Getters retu
 real shapes, seeded from the getter's name and how often it has been called, so that a getter moved against
 another one returns the same values.  With ``retry`` the stand-in flags status bit 4 on the chains of the second
 vintage on attempt 0 (Philox ids below 1_000_003).  The tool drives the three single-vintage samplers and the
-batch driver of the three models over their switches on the repository's FRED CSV (two late vintages,
+batch driver of the three ELB models over their switches (and of the standard VAR over a shorter list) on the
+repository's FRED CSV (two late vintages,
 MCMCdraws = fcstNdraws = 100, 4 horizons, chunk 40) and prints per configuration one digest of the call log and
 one of the returned arrays (the wall-clock fields of ``stats`` left out).
 
@@ -202,6 +203,15 @@ def make_fakes(pkg, rec):
                 out["crps"] = g.random(S)
             return out
 
+        def vma_summaries(self, *a, **k):
+            b = self._set("vma_summaries", *a, **k)
+            N, H_, nq = self.N, int(b["H"]), np.asarray(b["pct"], float).size
+            g = rec.rng("vma_summaries")
+            out = dict(median=g.standard_normal((N, N, H_)), quantiles=g.standard_normal((N, N, H_, nq)))
+            if b["ffr"] is not None:
+                out.update(sumMedian=g.standard_normal(N), sumQuantiles=g.standard_normal((N, nq)))
+            return out
+
         def close(self):
             self._set("close")
 
@@ -280,7 +290,7 @@ def batch(pkg, s, model, **kw):
     if kw.get("postprocess"):
         kw.setdefault("cumcode", d["cumcode"])
     fn = {"blockhybrid": S.goVARshadowrateBlockHybrid_batch, "hybrid": S.goVARhybrid_batch,
-          "shadowrate": S.goVARshadowrate_batch}[model]
+          "shadowrate": S.goVARshadowrate_batch, "standard": S.goVARstandard_batch}[model]
     return fn(d["data"], d["ydates"], s["ndxS"], s["ndxO"], s["mpm"], **kw)
 
 
@@ -323,6 +333,13 @@ def cpu_configs():
         for k, v in opts.items():
             cf[f"batch/{m}/{k}"] = ("batch", m, v)
     cf["single/blockhybrid/fcst1/C2/alternate"] = ("single", "blockhybrid", dict(fcst=True, nchains=2, alternate=True))
+    # goVAR.m's driver (model "standard": the linear chain set, no single-vintage wrapper of its own here)
+    for k, v in {"base": {}, "C1": dict(nchains=1), "post": dict(postprocess=True), "noroots": dict(maxlambda=False),
+                 "roots/host/post": dict(engine_roots="host", postprocess=True),
+                 "keep/post": dict(keep_draws=True, postprocess=True), "diag": dict(Compute_diagnostics=True),
+                 "stationarity": dict(check_stationarity=1), "vma": dict(doLoMem=False, sumFFRndx=0),
+                 "retry": dict(retry=True), "giveup": dict(retry=True, max_retries=0)}.items():
+        cf[f"batch/standard/{k}"] = ("batch", "standard", v)
     return cf
 
 
