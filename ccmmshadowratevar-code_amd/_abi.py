@@ -165,6 +165,9 @@ _SIGS = {
     "ccmm_vma_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_vma": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_vma_form": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _dp]),
+    "ccmm_cond_mean_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _ip]),
+    "ccmm_cond_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _ip]),
+    "ccmm_chains_cond_means": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]),
     "ccmm_chains_vma_summaries": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
                                             _dp, _dp, _ip]),
     "ccmm_diagnostics_host": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, _dp, _dp]),
@@ -320,6 +323,28 @@ def vma_host(PAI_all, N, p, H, return_info=False):
     out, info = _vma_out(M, int(N), int(H))
     _check(load_library().ccmm_vma_host(M, int(N), int(p), K, int(H), _ptr(P), _ptr(out), _ptr(info, _ip)),
            "ccmm_vma_host")
+    return (out, info) if return_info else out
+
+
+def _cond_mean_args(PAI_all, N, p, y0):
+    """(M, K, P, y0 as ny0 x N p C-contiguous, ny0, mean N x M column-major, info) of the cond_mean calls."""
+    M, K, P = _pai_batch(PAI_all, N, p)
+    y = np.ascontiguousarray(y0, dtype=np.float64)
+    if y.ndim == 1:
+        y = y[None]
+    if y.ndim != 2 or y.shape[1] != N * p or y.shape[0] not in (1, M):
+        raise ValueError(f"y0 must be N p or M x N p; got {np.shape(y0)} for M={M}, N={N}, p={p}")
+    return M, K, P, y, y.shape[0], np.zeros((N, M), order="F"), np.zeros(M, dtype=np.int32)
+
+
+def cond_mean_host(PAI_all, N, p, H, y0, return_info=False):
+    """ccmm_cond_mean_host: x_H(1:N) of x_0 = y0, x_{h+1} = c~ + comp x_h for each PAI (M x K x N), by the
+    library's fp64 recursion on the CPU (at most 16 threads; no GPU needed).  y0: N p (shared) or M x N p, p
+    blocks of N in the order of the companion state.  Returns N x M; info per matrix: 0, or 1 for a non-finite
+    entry in rows 0 .. N p (that column is NaN)."""
+    M, K, P, y, ny0, out, info = _cond_mean_args(PAI_all, int(N), int(p), y0)
+    _check(load_library().ccmm_cond_mean_host(M, int(N), int(p), K, int(H), _ptr(P), _ptr(y), ny0, _ptr(out),
+                                              _ptr(info, _ip)), "ccmm_cond_mean_host")
     return (out, info) if return_info else out
 
 
@@ -700,6 +725,14 @@ class Context:
                "ccmm_vma")
         return (out, info) if return_info else out
 
+    def cond_mean(self, PAI_all, N, p, H, y0, return_info=False):
+        """ccmm_cond_mean: as cond_mean_host, on the device for N <= 32 and N p <= 256 (the kernel k_cond_mean,
+        bit-identical to cond_mean_host), on the CPU otherwise."""
+        M, K, P, y, ny0, out, info = _cond_mean_args(PAI_all, int(N), int(p), y0)
+        _check(self.lib.ccmm_cond_mean(self.handle, M, int(N), int(p), K, int(H), _ptr(P), _ptr(y), ny0, _ptr(out),
+                                       _ptr(info, _ip)), "ccmm_cond_mean")
+        return (out, info) if return_info else out
+
     def vma_form(self, form, PAI_all, N, p, H):
         """ccmm_vma_form: as vma on the device range, by kernel form 0 (MFMA) or 1 (vector ALU; the same bits).
         Returns (N x N x H x M, device milliseconds of the kernel launches alone)."""
@@ -854,7 +887,7 @@ class Chains:
                "k_elb_prep", "k_elb_cond", "k_elb_gibbs", "k_elb_rebuild", "k_gram_chol_lag",
                "k_cta_solve_lag", "k_fcst", "k_gram_big", "k_chol_big", "k_cta_solve_big",
                "k_astep_big", "k_sv_big", "k_phi_big", "k_ps_chol", "k_ps_prop", "k_eig_maxroot",
-               "k_stat_select", "k_diag_series", "k_vma", "k_sum_ffr", "k_gather_pai", "k_post_stats")
+               "k_stat_select", "k_diag_series", "k_cond_mean", "k_vma", "k_sum_ffr", "k_gather_pai", "k_post_stats")
 
     def __init__(self, ctx: Context, *, N, p, T, B, ndata=1, model=MODEL_LINEAR, crn=False,
                  store_capacity=0, logy2offset=1e-3, seed=1012023, dPHI=None, Ns=0, elbTmax=0,
@@ -1031,6 +1064,21 @@ class Chains:
         nC = _check(self.lib.ccmm_chains_max_var_roots(self.handle, int(slot), _ptr(out), _ptr(info, _ip)),
                     "ccmm_chains_max_var_roots")
         return (out[:st * nC], info[:st * nC]) if return_info else out[:st * nC]
+
+    def cond_means(self, slot, H, y0, return_info=False):
+        """ccmm_chains_cond_means: the conditional mean path's end x_H(1:N) (cond_mean_host) of every stored PAI
+        draw of the chains bound to ``slot``, read in place on the device, one y0 (N p) for all; N x (stored C),
+        draw slowest, chain fastest (the order of max_var_roots).  The store is kept."""
+        st = self.stored()
+        y = np.ascontiguousarray(y0, dtype=np.float64).ravel()
+        if y.size != self.N * self.p:
+            raise ValueError(f"y0 must hold N p = {self.N * self.p} values; got {y.size}")
+        out = np.zeros((self.N, st * self.B), order="F")  # room for every chain; the call returns the slot's count
+        info = np.zeros(st * self.B, dtype=np.int32)
+        nC = _check(self.lib.ccmm_chains_cond_means(self.handle, int(slot), int(H), _ptr(y), _ptr(out),
+                                                    _ptr(info, _ip)), "ccmm_chains_cond_means")
+        out = np.asfortranarray(out[:, :st * nC])
+        return (out, info[:st * nC]) if return_info else out
 
     def vma_summaries(self, slot, H, pct, ffr=None, hslab=0):
         """ccmm_chains_vma_summaries: VMAmid / VMAtail (goVARshadowrateBlockHybrid.m:409-414) of the stored PAI
@@ -1294,11 +1342,20 @@ class Chains:
     def summaries(self, source, slot, rows=None, cumcode=None, realized=None, pct=(), floor_rows=None, floor=0.0):
         """Device summaries of the kept draws of data slot ``slot`` (ccmm_chains_summaries):
         source 0 paths / 1 censored paths (series = rows x H) / 2 PAI (K x N).  floor_rows (N
-        bools): those variables' paths floored at ``floor`` first (ccmm_chains_summaries_floor)."""
+        bools): those variables' paths floored at ``floor`` first (ccmm_chains_summaries_floor).
+        Sources 3 to 5 are the other draw stores, read in place: 3 sqrtht (series = Tmax x N, t fastest), 4
+        shadowrate_all and 5 missingrate_all (Ns x elbTmax, rate fastest; 5 only where missing rates were kept).
+        They take none of rows, cumcode, realized, floor_rows.  A series without a draw (t >= T of the slot, months
+        at or beyond its elbT) is NaN in every statistic; where some draws of a series are NaN, mean, median and
+        stdev are NaN and the quantiles are MATLAB's prctile over the other draws (NaN when there are none)."""
         N = self.N
         if source in (0, 1):
             nr = N if rows is None else int(np.count_nonzero(rows))
             S = nr * self.fH
+        elif source == 3:
+            S = self.T * N
+        elif source in (4, 5):
+            S = self.Ns * self.elbTmax
         else:
             S = self.K * N
         pct = _f(np.asarray(pct, float).ravel())

@@ -3,7 +3,8 @@
 // exports, profile), ccmm_chains_sweep.hip (the Gibbs blocks of a sweep), ccmm_chains_elb.hip (ELB step,
 // PS branch, treatment), ccmm_chains_fcst.hip (predictive density, summaries), ccmm_chains_eig.hip (maximum VAR
 // roots, check_stationarity), ccmm_chains_diag.hip (Compute_diagnostics of the stored draws), ccmm_chains_vma.hip
-// (impulse responses of the stored draws and their summaries).
+// (impulse responses of the stored draws and their summaries), ccmm_chains_condmean.hip (conditional mean paths of
+// the stored draws).
 #pragma once
 #include "ccmm_host.h"
 #include "ccmm_sweep.h"
@@ -202,6 +203,11 @@ struct __attribute__((visibility("hidden"))) ccmm_chains {
   // the segments and the sorted copy are postA / postB
   DBuf<double> vmaBuf;
   DBuf<int> vmaInfo;
+
+  // ---------------------------------------------------------------- conditional mean paths
+  // ccmm_chains_condmean.hip: the jump-off state, the mean of every stored draw (k_cond_mean) and the screen's flag
+  DBuf<double> cmY0, cmMean;
+  DBuf<int> cmInfo;
 
   // ---------------------------------------------------------------- profiling
   bool profiling = false;

@@ -176,7 +176,7 @@ void ccmm_chains::run_fcst(const RngArgs& ra) {
 // the statistics the caller asked for back on the host
 static void summarise(hipStream_t st, int S, int n, double* A, double* B, DBuf<char>& ws, DBuf<double>& out,
                       const double* realized, int nq, const double* pct, double* mean, double* median, double* quant,
-                      double* sdev, double* crps) {
+                      double* sdev, double* crps, bool nans = false) {
   const size_t wb = post_workspace_bytes(S, n);
   ws.alloc(wb);
   // device scratch: pct | realized | mean | median | sd | crps | quantiles
@@ -191,7 +191,7 @@ static void summarise(hipStream_t st, int S, int n, double* A, double* B, DBuf<c
   if (nq) HIPCHECK(hipMemcpy(dp, pct, nq * sizeof(double), hipMemcpyHostToDevice));
   if (realized) HIPCHECK(hipMemcpy(dr, realized, S * sizeof(double), hipMemcpyHostToDevice));
   HIPCHECK(post_summaries(st, S, n, A, B, ws.p, wb, realized ? dr : nullptr, nq, dp,
-                          dm, dmed, nq ? dq : nullptr, dsd, crps ? dcr : nullptr));
+                          dm, dmed, nq ? dq : nullptr, dsd, crps ? dcr : nullptr, nans));
   HIPCHECK(hipStreamSynchronize(st));
   auto get = [&](double* dst, const double* src, size_t cnt) {
     if (dst) HIPCHECK(hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost));
@@ -250,8 +250,43 @@ void ccmm_chains::summaries(int source, int sl, const uint8_t* rows, const uint8
     n = C * stored;
     postA.alloc((size_t)S * n);
     HIPCHECK(post_gather_pai(ctx->stream, sPAI.p, c0, C, stored, cfg.store_capacity, K * N, postA.p));
+  } else if (source >= 3 && source <= 5) {
+    // the other draw stores, [chain][capacity][entry] as sPAI: 3 sqrtht (Tmax x N, t fastest), 4 shadowrate_all and
+    // 5 missingrate_all (Ns x elbTmax, rate fastest).  Their draws may be NaN (shadowrate_all under the missing-data
+    // treatment, missingrate_all of a sweep without a PS proposal): the NaN rules of post_summaries
+    require(!rows && !cumcode && !flo && !realized && !crps,
+            "sources 3 to 5 take no rows, cumcode, floor, realized values or crps");
+    require(stored > 0 && sPAI.p, "no stored draws");
+    const double* src = sSqrtht.p;
+    S = cfg.T * N;
+    if (source != 3) {
+      require(bh && cfg.elbTmax > 0 && sShadow.p, "no stored shadow rates");
+      require(have_elb_slot[sl], "ccmm_chains_set_elb_slot was not called for the slot");
+      require(source == 4 || (keep_first && sMissing.p), "source 5: missing rates were not kept");
+      src = source == 4 ? sShadow.p : sMissing.p;
+      S = cfg.Ns * cfg.elbTmax;
+    }
+    require(src != nullptr && S > 0, "no stored draws of the source");
+    n = C * stored;
+    postA.alloc((size_t)S * n);
+    HIPCHECK(post_gather_pai(ctx->stream, src, c0, C, stored, cfg.store_capacity, S, postA.p));
+    postB.alloc((size_t)S * n);
+    summarise(ctx->stream, S, n, postA.p, postB.p, postWs, postOut, nullptr, nq, pct, mean, median, quant, sdev, nullptr,
+              true);
+    // the series that hold no draw (t >= T of the slot; months at or beyond its elbT): NaN in every statistic
+    const double nan = std::nan("");
+    for (int e = 0; e < S; ++e) {
+      const bool live = source == 3 ? e % cfg.T < hT[sl] : e / cfg.Ns < hElbT[sl];
+      if (live) continue;
+      for (double* o : {mean, median, sdev})
+        if (o) o[e] = nan;
+      if (quant)
+        for (int q = 0; q < nq; ++q) quant[(size_t)q * S + e] = nan;
+    }
+    return;
   } else {
-    throw ArgError("source must be 0 (paths), 1 (censored paths) or 2 (PAI draws)");
+    throw ArgError("source must be 0 (paths), 1 (censored paths), 2 (PAI draws), 3 (sqrtht), 4 (shadowrate_all) or "
+                   "5 (missingrate_all)");
   }
   postB.alloc((size_t)S * n);
   summarise(ctx->stream, S, n, postA.p, postB.p, postWs, postOut, realized, nq, pct, mean, median, quant, sdev,

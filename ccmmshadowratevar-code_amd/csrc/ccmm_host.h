@@ -106,6 +106,7 @@ enum KernelId {
   KID_EIG,
   KID_STATSEL,
   KID_DIAG,
+  KID_CONDMEAN,
   KID_VMA,
   KID_SUMFFR,
   KID_POSTGATHER,

@@ -56,6 +56,29 @@ __device__ __forceinline__ double hazen_index(int n, double pc) {
   return ((double)n * q + 0.5) - 1.0;
 }
 
+// MATLAB prctile at percentile pc of the n sorted values x
+__device__ __forceinline__ double prctile_sorted(const double* __restrict__ x, int n, double pc) {
+  const double vi = hazen_index(n, pc);
+  const double fl = floor(vi);
+  int lo = (int)fl, hi = lo + 1;
+  double gam = vi - fl;
+  if (vi < 0.0) {
+    lo = hi = 0;
+    gam = 0.0;
+  }
+  if (lo >= n - 1) {
+    lo = hi = n - 1;
+    gam = 0.0;
+  }
+  return lerp_np(x[lo], x[hi], gam);
+}
+
+// NANS: the series may hold NaN draws (the draw stores of sources 3 to 5), which follow MATLAB: mean, sd and
+// median are NaN as soon as one draw is NaN; the quantiles are prctile over the other draws, NaN when there are
+// none.  The radix sort over all 64 key bits puts the NaNs with the sign bit set first and the others last, so the
+// values are the run [lead, lead + n) of the segment.  A series without a NaN takes the statements of the
+// NANS = false kernel, whose bits the summaries of sources 0 to 2 keep.
+template <bool NANS>
 __global__ __launch_bounds__(256) void k_post_stats(int S, int n, const double* __restrict__ sorted,
                                                     const double* __restrict__ realized, int nq,
                                                     const double* __restrict__ pct, double* mean,
@@ -66,6 +89,31 @@ __global__ __launch_bounds__(256) void k_post_stats(int S, int n, const double* 
   if (s >= S) return;
   const double* x = sorted + (size_t)s * n;
   const int tid = threadIdx.x;
+  if constexpr (NANS) {
+    double nn = 0.0, nl = 0.0;  // counts, exact in fp64
+    for (int i = tid; i < n; i += 256) {
+      const double v = x[i];
+      if (v != v) {
+        nn += 1.0;
+        if (__double2hiint(v) < 0) nl += 1.0;
+      }
+    }
+    const int nans = (int)block_sum_256(nn, red), lead = (int)block_sum_256(nl, red);
+    if (nans > 0) {
+      const double nan = __builtin_nan("");
+      if (tid == 0) {
+        if (mean) mean[s] = nan;
+        if (sd) sd[s] = nan;
+        if (median) median[s] = nan;
+        if (crps) crps[s] = nan;
+      }
+      x += lead;
+      n -= nans;
+      if (quant)
+        for (int q = tid; q < nq; q += 256) quant[(size_t)q * ldq + s] = n > 0 ? prctile_sorted(x, n, pct[q]) : nan;
+      return;
+    }
+  }
   double a = 0.0;
   for (int i = tid; i < n; i += 256) a += x[i];
   const double mu = block_sum_256(a, red) / n;
@@ -90,25 +138,10 @@ __global__ __launch_bounds__(256) void k_post_stats(int S, int n, const double* 
     if (mean) mean[s] = mu;
     if (sd) sd[s] = sqrt(var);
   }
-  auto pq = [&](double pc) {
-    const double vi = hazen_index(n, pc);
-    const double fl = floor(vi);
-    int lo = (int)fl, hi = lo + 1;
-    double gam = vi - fl;
-    if (vi < 0.0) {
-      lo = hi = 0;
-      gam = 0.0;
-    }
-    if (lo >= n - 1) {
-      lo = hi = n - 1;
-      gam = 0.0;
-    }
-    return lerp_np(x[lo], x[hi], gam);
-  };
   // median: the middle value, or the mean of the middle pair (MATLAB median, numpy median)
   if (median && tid == 0) median[s] = (n & 1) ? x[n / 2] : (x[n / 2 - 1] + x[n / 2]) / 2.0;
   if (quant)
-    for (int q = tid; q < nq; q += 256) quant[(size_t)q * ldq + s] = pq(pct[q]);
+    for (int q = tid; q < nq; q += 256) quant[(size_t)q * ldq + s] = prctile_sorted(x, n, pct[q]);
 }
 
 // forecast paths: chain c's record of kept draw m, forecast draw job, horizon h, variable i
@@ -185,7 +218,7 @@ size_t post_workspace_bytes(int S, int n) {
 
 hipError_t post_summaries(hipStream_t st, int S, int n, const double* draws, double* sorted, void* ws,
                           size_t ws_bytes, const double* realized, int nq, const double* pct, double* mean,
-                          double* median, double* quant, double* sd, double* crps) {
+                          double* median, double* quant, double* sd, double* crps, bool nans) {
   if (S <= 0 || n <= 0) return hipSuccess;
   const size_t per = series_per_sort(S, n);
   int* off = (int*)ws;
@@ -198,9 +231,9 @@ hipError_t post_summaries(hipStream_t st, int S, int n, const double* draws, dou
     PCHECK(rocprim::segmented_radix_sort_keys(tmp, tb, draws + s0 * n, sorted + s0 * n,
                                               (unsigned int)((size_t)Sc * n), (unsigned int)Sc, off, off + 1, 0, 64,
                                               st));
-    PCHECK(launch_k(k_post_stats, dim3(Sc), dim3(256), 0, false, st, Sc, n, sorted + s0 * n,
-                    realized ? realized + s0 : nullptr, nq, pct, at(mean, s0), at(median, s0), at(quant, s0), (size_t)S,
-                    at(sd, s0), at(crps, s0)));
+    PCHECK(launch_k(nans ? k_post_stats<true> : k_post_stats<false>, dim3(Sc), dim3(256), 0, false, st, Sc, n,
+                    sorted + s0 * n, realized ? realized + s0 : nullptr, nq, pct, at(mean, s0), at(median, s0),
+                    at(quant, s0), (size_t)S, at(sd, s0), at(crps, s0)));
   }
   return hipSuccess;
 }

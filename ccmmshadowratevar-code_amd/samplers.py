@@ -21,7 +21,8 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _abi
-from .model import build_bh, build_hybrid, build_var, elbT0_of, initial_state
+from .model import (build_bh, build_hybrid, build_var, elbT0_of, initial_state, setMinnesotaMean,
+                    setShadowYields)
 
 _CTX = {}
 
@@ -1697,3 +1698,261 @@ def generateGIRF(data, ydates, irfDate, PAI_all, invA_all, PHI_all, sqrtht_all, 
     res["IRF1plus"], res["IRF1plusTails"] = med_tails(plus - base)       # :268-276
     res["IRF1minus"], res["IRF1minusTails"] = med_tails(minus - base)
     return res
+
+
+# ---------------------------------------------------------------------------
+# Shadow-rate against missing-data sampling of one full-sample vintage (doVARshadowrateBlockHybridMissingData.m,
+# doVARshadowrateMissingData.m, doVARshadowrateFullyHybridMissingData.m) on the device
+
+DO_TAILS = np.array([5.0, 25.0, 75.0, 95.0])                      # :235
+DO_MODELLABELS = {"blockhybrid": "BlockHybridShadowVsMissingRateSampling",           # :133
+                  "shadowrate": "ShadowVsMissingRateSampling",
+                  "hybrid": "FullyHybridShadowVsMissingRateSampling"}
+DO_MEAN_KEYS = ("shadowMean", "missingMean", "shadowMeanMedian", "missingMeanMedian", "maxH", "meanjumpoff")
+# the labs run side by side only up to this many chains each: k_elb_gibbs_mp and the split solve spin-wait across
+# compute units and count the workgroups of their own chain set alone, so two sets must leave each other room
+# (16 chains per lab hold at most 64 of the 256 compute units in waiting workgroups)
+DO_CONCURRENT_MAX_CHAINS = 16
+
+
+def cond_mean_y0(data, meanjumpoff, p):
+    """YdataELB(:) of doVARshadowrateBlockHybridMissingData.m:436, YdataELB = data(meanjumpoff-(p-1):meanjumpoff,:)',
+    for the 1-based row ``meanjumpoff``: N p values, the p months oldest first, the N variables within a month.
+    The companion state is newest month first, so the reference multiplies lag 1 by the oldest of the p months;
+    cond_mean_host takes the state as given, and the driver reproduces the reference as written."""
+    mj, p = int(meanjumpoff), int(p)
+    rows = np.asarray(data, float)[mj - p:mj]             # MATLAB rows mj-(p-1) .. mj
+    if mj - p < 0 or rows.shape[0] != p:
+        raise ValueError(f"meanjumpoff = {mj} leaves no {p} months of data before it")
+    return np.ascontiguousarray(rows).ravel()             # (rows')(:): month by month
+
+
+def _do_treatment(model, doELBsampling):
+    """(missing, alternate) as the model's sampler sets them when the scripts call it with doELBsampling and
+    doELBsampleAlternate = true (mcmcVARshadowrate takes no such flag, mcmcVARhybridGibbs ignores it when it
+    samples the shadow rates; without sampling the one unconstrained draw is the data either way)."""
+    return (not doELBsampling), bool(doELBsampling and model == "blockhybrid")
+
+
+def do_concurrent(concurrent, nchains):
+    """Whether doVARMissingData runs its two labs side by side."""
+    return bool(concurrent) and int(nchains) <= DO_CONCURRENT_MAX_CHAINS
+
+
+def _do_lab(model, bm, lab, ctx, *, C, MCMCdraws, burn, seed, ELBbound, ndxYIELDS, check_stationarity, pct, y0,
+            maxH, keep_draws):
+    """One lab (0: the shadow rates are sampled; 1: the ELB months are missing data) of doVARMissingData on
+    context ``ctx``: the sampler's chain set, then every summary from its draw stores in place."""
+    spec = _MODELS[model]
+    t0 = time.perf_counter()
+    ch, _, _ = _bh_chain_set(ctx, [(None, bm, None)], C, seed=seed, ids=(lab * C + np.arange(C)).astype(np.uint32),
+                             store_capacity=MCMCdraws, gibbsburn=100, ELBbound=ELBbound, ndxYIELDS=ndxYIELDS,
+                             model=model)
+    missing, alternate = _do_treatment(model, lab == 0)
+    use_ps = _bh_switches(ch, spec, burn, Nproposals=spec.Nproposals, missing=missing, alternate=alternate,
+                          keep_missingrate=spec.ps_missingrate, check_stationarity=check_stationarity)
+    _run_chain_set(ch, burn, MCMCdraws, False)
+    out = dict(stats={})
+    _stationarity_stats(ch, check_stationarity, out["stats"])
+    out["status"] = ch.get_status()
+    m = bm.var
+    Ns, elbT, nq = len(bm.ndxS), bm.elbT, len(pct)
+    kept = missing or alternate or (use_ps and spec.ps_missingrate)       # as _run_single
+
+    def rates(source):                                    # Ns x elbTmax, rate fastest -> elbT x Ns [x 4]
+        if source is None or not elbT:
+            return np.full((elbT, Ns), np.nan), np.full((elbT, Ns, DO_TAILS.size), np.nan)
+        s = ch.summaries(source, 0, pct=DO_TAILS)
+        mid = s["median"].reshape(Ns, -1, order="F")[:, :elbT].T
+        tails = s["quantiles"].reshape(Ns, -1, DO_TAILS.size, order="F")[:, :elbT].transpose(1, 0, 2)
+        return np.ascontiguousarray(mid), np.ascontiguousarray(tails)
+
+    out["shadowrate"] = rates(4)
+    out["missingrate"] = rates(5 if kept else None)
+    pa = ch.summaries(2, 0)
+    out["PAI"] = {k: pa[k].reshape(m.K, m.N, order="F") for k in ("mean", "median", "stdev")}
+    sv = ch.summaries(3, 0, pct=pct)                      # Tmax x N, t fastest (Tmax = T: one slot)
+    out["SVmid"] = sv["median"].reshape(m.T, m.N, order="F")
+    out["SVtails"] = np.ascontiguousarray(np.moveaxis(sv["quantiles"].reshape(m.T, m.N, nq, order="F"), 2, 0))
+    if y0 is not None:
+        ch.profile(True)                                  # the kernel's device time, for stats
+        out["mean"] = ch.cond_means(0, maxH, y0)
+        out["stats"]["k_cond_mean_ms"] = ch.kernel_times()["k_cond_mean"][0]
+        ch.profile(False)
+    if use_ps:
+        ps = ch.get_ps()
+        out["countELBaccept"] = ps["countAccept"] + ps["countAcceptBurnin"] if model == "hybrid" else ps["countAccept"]
+    if keep_draws:                                        # after the summaries: get_draws empties the store
+        d = ch.get_draws(("PAI_all", "sqrtht_all"))
+        out["PAI_all"], out["SV_all"] = d["PAI_all"], d["sqrtht_all"]
+    ch.close()
+    out["seconds"] = time.perf_counter() - t0
+    return out
+
+
+def _do_scatter(y, x):
+    """scatter = ols(y, [1 x]) of :348 (jplv ols.m): beta, yhat, resid, sige, rsqr, nobs, nvar."""
+    X = np.column_stack([np.ones_like(x), x])
+    beta = np.linalg.lstsq(X, y, rcond=None)[0]
+    yhat = X @ beta
+    resid = y - yhat
+    ym = y - y.mean()
+    return dict(beta=beta, yhat=yhat, resid=resid, sige=float(resid @ resid) / (y.size - 2),
+                rsqr=1.0 - float(resid @ resid) / float(ym @ ym), nobs=y.size, nvar=2)
+
+
+def doVARMissingData(model, data, ydates, ncode, *, jumpoffDate=None, p=12, np_=12, MCMCdraws=1000, ELBbound=0.25,
+                     doRATSprior=True, check_stationarity=0, seed=1012023, nchains=1, setQuantiles=SET_QUANTILES,
+                     maxH=12, keep_draws=False, concurrent=True, device=0, burnin=None):
+    """doVARshadowrateBlockHybridMissingData.m (model="blockhybrid"), doVARshadowrateMissingData.m ("shadowrate")
+    and doVARshadowrateFullyHybridMissingData.m ("hybrid"): the vintage that ends at ``jumpoffDate`` (a datenum of
+    ``ydates``; None: the last month) estimated twice, lab 1 sampling the shadow rates (doELBsampling = true) and lab
+    2 treating the ELB months as missing data (doELBsampling = false), and the two posteriors compared.  Every
+    summary is taken on the device from the draw stores in place (Chains.summaries sources 2 to 5,
+    Chains.cond_means), pooled over the ``nchains`` chains of a lab; only summaries are downloaded.
+
+    Lab l (0, 1), chain c draws the Philox stream l nchains + c of ``seed``: the reference gives each lab its own
+    stream.  No predictive density (the scripts take six outputs).  ``concurrent`` runs the labs as spmd(2) does,
+    each on its own context (stream) and host thread, for nchains <= 16; more chains run one lab after the other
+    whatever the flag says.  Both forms give the same bits.
+
+    Returns a dict under the scripts' names (:223-244, 289-290, 348, 399-403, 433-478), 0-based where Python
+    indexes and MATLAB's values for elbT0, ELBjumpoff = p + elbT0 and meanjumpoff = ELBjumpoff + 6 (1-based rows):
+    shadowrateMid / missingrateMid / missingrate2Mid (elbT x Ns) and *Tails (elbT x Ns x 4, percentiles 5 25 75 95;
+    missingrate* of lab 1 are NaN where a kept sweep made no such draw, by MATLAB's rules), medianPAIshadow,
+    medianPAImissing, PAI0, PAI0se, PAImean, PAIdevs (K x N), scatter (the OLS of :348, on the host), shadowSVmid /
+    missingSVmid (T x N) and *SVtails (nq x T x N), shadowMean / missingMean (N x MCMCdraws nchains, draw slowest) with
+    shadowMeanMedian / missingMeanMedian (N; the medians :470 prints), maxH and meanjumpoff -- absent for "hybrid",
+    whose script has that block commented out -- countELBaccept (lab 1, per chain), status (2 x nchains) and
+    stats (seconds per lab and in all, stationarityRedraws, concurrent).  The jump-off state of the means is
+    cond_mean_y0: as the reference writes it, oldest month first against a newest-first companion state.
+    ``keep_draws`` adds PAIshadow, PAImissing (M x K x N [x nchains]) and SVshadow, SVmissing (M x T x N [x nchains]),
+    downloaded after the summaries.  The VMA loop of doVARshadowrateMissingData.m:188-213 feeds nothing the
+    script keeps and is not run."""
+    if model not in DO_MODELLABELS:
+        raise ValueError(f"model must be one of {sorted(DO_MODELLABELS)}, not {model!r}")
+    spec = _MODELS[model]
+    data = np.asarray(data, float)
+    ydates = np.asarray(ydates, float)
+    N, C, M = data.shape[1], int(nchains), int(MCMCdraws)
+    if jumpoffDate is None:
+        thisT = len(ydates)
+    else:
+        hit = np.flatnonzero(ydates == jumpoffDate)
+        if hit.size != 1:
+            raise ValueError("jumpoffDate is not one of ydates")
+        thisT = int(hit[0]) + 1                                                  # :151, 1-based
+    ndxS, ndxO, ndxY = setShadowYields(ncode, ELBbound)
+    if ndxS.size == 0:
+        raise ValueError("no shadow-rate variable among ncode")
+    elbT0 = elbT0_of(data, ndxS, ELBbound, p)                                    # :113-114
+    block = ~_mask(N, ndxS)                                                      # :149
+    bm = spec.build(thisT, p, np_, data, ydates, ndxS, ndxO, setMinnesotaMean(ncode), ELBbound, elbT0,
+                    doRATSprior, block)
+    if getattr(bm, "warn_elbT0", False):
+        warnings.warn("elbT0 + 1 should be a missing obs, but it is not ...")
+    if check_stationarity and not spec.stationarity:
+        warnings.warn("no stationarity check for hybrid model")
+        check_stationarity = 0
+    burn = M if burnin is None else int(burnin)
+    pct = np.asarray(setQuantiles, float).ravel()
+    ELBjumpoff = p + elbT0                                                       # :250
+    means = model != "hybrid"
+    meanjumpoff = ELBjumpoff + 6                                                 # :435
+    y0 = cond_mean_y0(data, meanjumpoff, p) if means else None
+    kw = dict(C=C, MCMCdraws=M, burn=burn, seed=seed, ELBbound=ELBbound, ndxYIELDS=ndxY,
+              check_stationarity=check_stationarity, pct=pct, y0=y0, maxH=int(maxH), keep_draws=keep_draws)
+    side = do_concurrent(concurrent, C)
+    labs = [None, None]
+    t0 = time.perf_counter()
+    if side:
+        import threading
+        errs = []
+
+        def run(lab):
+            ctx = None
+            try:
+                ctx = _abi.Context(device)                # its own stream
+                labs[lab] = _do_lab(model, bm, lab, ctx, **kw)
+            except BaseException as e:  # noqa: BLE001
+                errs.append(e)
+            finally:
+                if ctx is not None:
+                    ctx.close()
+        th = [threading.Thread(target=run, args=(lab,)) for lab in (0, 1)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        if errs:
+            raise errs[0]
+    else:
+        for lab in (0, 1):
+            labs[lab] = _do_lab(model, bm, lab, context(device), **kw)
+    total = time.perf_counter() - t0
+    sh, mi = labs
+    res = dict(model=model, thisT=thisT, T=thisT - p, elbT0=elbT0, ELBjumpoff=ELBjumpoff, setQuantiles=pct,
+               ndxSHADOWRATE=ndxS, ndxOTHERYIELDS=ndxO, actualrateBlock=block)
+    res["shadowrateMid"], res["shadowrateTails"] = sh["shadowrate"]
+    res["missingrateMid"], res["missingrateTails"] = sh["missingrate"]
+    res["missingrate2Mid"], res["missingrate2Tails"] = mi["missingrate"]
+    res["medianPAIshadow"], res["medianPAImissing"] = sh["PAI"]["median"], mi["PAI"]["median"]
+    res["scatter"] = _do_scatter(res["medianPAIshadow"].ravel(order="F"), res["medianPAImissing"].ravel(order="F"))
+    res["PAI0"], res["PAI0se"], res["PAImean"] = mi["PAI"]["mean"], mi["PAI"]["stdev"], sh["PAI"]["mean"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        res["PAIdevs"] = (res["PAImean"] - res["PAI0"]) / res["PAI0se"]          # :403
+    res["shadowSVmid"], res["shadowSVtails"] = sh["SVmid"], sh["SVtails"]
+    res["missingSVmid"], res["missingSVtails"] = mi["SVmid"], mi["SVtails"]
+    if means:
+        res.update(maxH=int(maxH), meanjumpoff=meanjumpoff, shadowMean=sh["mean"], missingMean=mi["mean"],
+                   shadowMeanMedian=np.median(sh["mean"], axis=1), missingMeanMedian=np.median(mi["mean"], axis=1))
+    res["countELBaccept"] = sh.get("countELBaccept")
+    res["status"] = np.stack([sh["status"], mi["status"]])
+    if keep_draws:
+        drop = (lambda a: a[..., 0]) if C == 1 else (lambda a: a)
+        res.update(PAIshadow=drop(sh["PAI_all"]), PAImissing=drop(mi["PAI_all"]), SVshadow=drop(sh["SV_all"]),
+                   SVmissing=drop(mi["SV_all"]))
+    res["stats"] = dict(seconds=[sh["seconds"], mi["seconds"]], seconds_total=total, concurrent=side,
+                        stationarityRedraws=[lab["stats"].get("stationarityRedraws") for lab in labs],
+                        k_cond_mean_ms=[lab["stats"].get("k_cond_mean_ms") for lab in labs])
+    return res
+
+
+def save_do_mat(filename, res, *, data, ydates, ncode, tcode, cumcode, p=12, MCMCdraws, ELBbound=0.25,
+                datalabel="fredblockMD20-2022-09", doRATSprior=True):
+    """The result file of the doVAR*MissingData scripts (:501-509, save('do-<titlename>.mat', ...)) from a
+    doVARMissingData result, as a v5 MAT-file (scipy.io.savemat) under the workspace's names.  ``filename`` None:
+    do-<titlename>.mat in the working directory, titlename as :138.  Index variables are 1-based as in MATLAB.
+    Returns (the file's name, the sorted variable names)."""
+    from scipy.io import savemat
+    model = res["model"]
+    modellabel = DO_MODELLABELS[model] + ("-RATSbvarshrinkage" if doRATSprior else "")
+    tags = {0.25: "", 0.125: "-ELB125", 0.5: "-ELB500"}                         # :59-68
+    if ELBbound not in tags:
+        raise ValueError(f"ELBbound value of {ELBbound:5.2f} not recognized")
+    titlename = f"{datalabel}{tags[ELBbound]}-{modellabel}-p{p}"
+    if filename is None:
+        filename = f"do-{titlename}.mat"
+    data = np.asarray(data, float)
+    ndxS1 = np.asarray(res["ndxSHADOWRATE"], int) + 1
+    ndxO1 = np.asarray(res["ndxOTHERYIELDS"], int) + 1
+    m = dict(data=data, ydates=np.asarray(ydates, float)[:, None], p=float(p), np=12.0, N=float(data.shape[1]),
+             ncode=np.array(list(ncode), dtype=object)[None, :], tcode=np.asarray(tcode, float)[None, :],
+             cumcode=np.asarray(cumcode, bool)[None, :], MCMCdraws=float(MCMCdraws), ELBbound=float(ELBbound),
+             ELBdummy=data[:, ndxS1 - 1] <= ELBbound, ndxSHADOWRATE=ndxS1.astype(float)[None, :],
+             ndxOTHERYIELDS=ndxO1.astype(float)[None, :], ndxYIELDS=np.union1d(ndxS1, ndxO1).astype(float)[None, :],
+             actualrateBlock=np.asarray(res["actualrateBlock"], bool)[None, :], datalabel=datalabel,
+             modellabel=modellabel, titlename=titlename, thisT=float(res["thisT"]), T=float(res["T"]),
+             elbT0=float(res["elbT0"]), ELBjumpoff=float(res["ELBjumpoff"]),
+             setQuantiles=np.asarray(res["setQuantiles"], float)[None, :], doRATSprior=bool(doRATSprior))
+    for k, v in res.items():
+        if k in ("stats", "status", "model") or k in m or v is None:
+            continue
+        if k == "scatter":
+            m[k] = {a: (np.asarray(b, float)[:, None] if np.ndim(b) == 1 else float(b)) for a, b in v.items()}
+        elif isinstance(v, np.ndarray):
+            m[k] = v[:, None] if v.ndim == 1 else v
+        else:
+            m[k] = float(v)
+    savemat(filename, m, do_compression=True)
+    return filename, sorted(m)

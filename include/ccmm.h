@@ -518,8 +518,19 @@ int ccmm_draw_summaries(ccmm_ctx* ctx, int S, int n, const double* draws, const 
  *             kept records x Nd
  *   source 1  censored forecast paths (linear fcstYcensorDraws, block hybrid fcstYdraws)
  *   source 2  PAI draws, series = K x N, draws = chains x stored draws
+ *   source 3  sqrtht draws, series = Tmax x N (t fastest); a series at t >= T of the slot holds no draw
+ *   source 4  shadowrate_all, series = Ns x elbTmax (rate fastest); the months at or beyond the slot's elbT
+ *             hold no draw
+ *   source 5  missingrate_all, as source 4; an argument error unless missing rates were kept
+ *             (ccmm_chains_keep_missingrate, or the missing / alternate treatment of the ELB months)
  * rows: N bytes selecting the variables (NULL: all); cumcode: N bytes, cumsum over the
- * horizons for those variables first (:353-355; NULL: none). */
+ * horizons for those variables first (:353-355; NULL: none).
+ * Sources 3 to 5 (doVARshadowrateBlockHybridMissingData.m:223-244, 475-478) read the store in place and take
+ * no rows, cumcode, realized, crps or floor: passing one is an argument error.  A series without a draw is NaN
+ * in every statistic.  Their draws may be NaN (shadowrate_all under the missing-data treatment, missingrate_all
+ * of a kept sweep without a PS proposal) and then follow MATLAB: mean, stdev and median are NaN as soon as one
+ * draw of the series is NaN; the quantiles are prctile over the other draws, NaN when there are none.  Sources 0
+ * to 2 run the kernel without these rules, as before. */
 int ccmm_chains_summaries(ccmm_chains* ch, int source, int slot, const uint8_t* rows, const uint8_t* cumcode,
                           const double* realized, int nq, const double* pct, double* mean, double* median,
                           double* quantiles, double* stdev, double* crps);
@@ -586,6 +597,33 @@ int ccmm_vma_form(ccmm_ctx* ctx, int form, int M, int N, int p, int K, int H, co
 int ccmm_chains_vma_summaries(ccmm_chains* ch, int slot, int H, int hslab, int nq, const double* pct,
                               double* vmaMedian, double* vmaQuantiles, int ffr, double* sumMedian,
                               double* sumQuantiles, int* nbad);
+
+/* ------------------------------------------------------------ conditional mean paths
+ * thatMean of doVARshadowrateBlockHybridMissingData.m:433-468 (and doVARshadowrateMissingData.m) for each of M
+ * coefficient matrices: x_H(1:N) of the recursion x_0 = y0, x_{h+1} = c~ + comp x_h with comp the N p x N p
+ * companion matrix and c~ = [PAI(0,:)'; 0].  The reference writes ((I - comp) \ (I - comp^H)) c~ + comp^H y0, the
+ * same vector whenever I - comp is nonsingular; cond(I - comp) is 2-3e6 on the reference's data, so the recursion
+ * is also the more accurate form.  PAI as for the maximum root (K x N column-major, K >= 1 + N p; rows beyond
+ * 1 + N p are ignored).  y0: ny0 x N p doubles, p blocks of N in the order of the companion state (block 0 is
+ * multiplied by lag 1), whatever they hold; ny0 = 1 (one y0 for all draws) or M.  The reference fills y0 with
+ * YdataELB(:), YdataELB = data(meanjumpoff-(p-1):meanjumpoff,:)', which is oldest month first while the
+ * companion state is newest first; the functions here take y0 as given, and samplers.doVARMissingData builds it
+ * as the reference writes it.  Every equation of a step is one fp64 fused multiply-add chain that starts from the
+ * intercept and runs over the state ascending.  mean: N x M doubles (mean[m N + i]).  info: M ints, 0, or 1 for a
+ * NaN or Inf among rows 0 .. N p of the matrix (that draw's mean is NaN); may be NULL.  A non-finite y0 is an
+ * argument error. */
+/* On the CPU (at most 16 threads); needs no context and no GPU. */
+int ccmm_cond_mean_host(int M, int N, int p, int K, int H, const double* PAI, const double* y0, int ny0,
+                        double* mean, int* info);
+/* Host inputs; on the device for N <= 32 and N p <= 256 (one wave per matrix, bit-identical to the host
+ * function), on the CPU for any larger shape. */
+int ccmm_cond_mean(ccmm_ctx* ctx, int M, int N, int p, int K, int H, const double* PAI, const double* y0, int ny0,
+                   double* mean, int* info);
+/* The stored PAI draws of the chains bound to data slot `slot` (contiguous chain indices), read in place, one
+ * y0 (N p doubles) for all: mean[(m C + c) N + i] for stored draw m and the slot's c-th chain, the order of
+ * ccmm_chains_max_var_roots; info likewise or NULL.  Returns C (> 0), or a negative error code.  The draw store
+ * is left as it is. */
+int ccmm_chains_cond_means(ccmm_chains* ch, int slot, int H, const double* y0, double* mean, int* info);
 
 /* check_stationarity (mcmcVAR.m:221-232, mcmcVARshadowrateBlockHybrid.m:333-347): with enable != 0 every
  * sweep computes the maximum VAR root of each chain's new PAI after the coefficient block and, while a chain's
