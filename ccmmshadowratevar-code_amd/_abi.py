@@ -155,6 +155,11 @@ _SIGS = {
     "ccmm_girf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
                             _dp, C.c_int, _u8p, _u8p, C.c_double, _u8p, C.c_double, C.c_double, _dp,
                             _dp, C.c_uint64, _dp]),
+    "ccmm_chains_girf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _u8p,
+                                   C.c_double, _u8p, C.c_uint64, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp,
+                                   _dp, _dp, _dp, _ip]),
+    "ccmm_chains_girf_inputs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _u8p, _dp, _dp, _dp, _ip]),
+    "ccmm_chains_poke_stored_phi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
     "ccmm_chains_summaries": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, _u8p, _dp, C.c_int, _dp,
                                         _dp, _dp, _dp, _dp, _dp]),
     "ccmm_chains_summaries_floor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, _u8p, _u8p, C.c_double, _dp,
@@ -887,7 +892,7 @@ class Chains:
                "k_elb_prep", "k_elb_cond", "k_elb_gibbs", "k_elb_rebuild", "k_gram_chol_lag",
                "k_cta_solve_lag", "k_fcst", "k_gram_big", "k_chol_big", "k_cta_solve_big",
                "k_astep_big", "k_sv_big", "k_phi_big", "k_ps_chol", "k_ps_prop", "k_eig_maxroot",
-               "k_stat_select", "k_diag_series", "k_cond_mean", "k_vma", "k_sum_ffr", "k_gather_pai", "k_post_stats")
+               "k_stat_select", "k_diag_series", "k_girf_prep", "k_girf", "k_girf_rb", "k_girf_collect", "k_cond_mean", "k_vma", "k_sum_ffr", "k_gather_pai", "k_post_stats")
 
     def __init__(self, ctx: Context, *, N, p, T, B, ndata=1, model=MODEL_LINEAR, crn=False,
                  store_capacity=0, logy2offset=1e-3, seed=1012023, dPHI=None, Ns=0, elbTmax=0,
@@ -1101,6 +1106,116 @@ class Chains:
         if nbad.value > 0:
             raise RuntimeError(f"ccmm_chains_vma_summaries: {nbad.value} stored draws hold a NaN or Inf coefficient")
         return out
+
+    GIRF_SETS = ("fcstYhat", "fcstYhat1plus", "fcstYhat1minus", "IRF1plus", "IRF1minus")
+    GIRF_RB_SETS = ("YhatRB", "IRF1RB")
+
+    def _girf_args(self, jump, ndxYields):
+        """(jump p x N C-contiguous, ndxYields as N bytes or None, Ny) of the girf calls."""
+        j = np.ascontiguousarray(jump, dtype=np.float64)
+        if j.shape != (self.p, self.N):
+            raise ValueError(f"jump must be p x N = {self.p} x {self.N} (the months t0, t0 - 1, ..); got {j.shape}")
+        yl = None
+        if self.model != MODEL_LINEAR:
+            if ndxYields is None:
+                raise ValueError("the shadow-rate models need ndxYields")
+            yl = np.ascontiguousarray(np.asarray(ndxYields, bool), dtype=np.uint8)
+            if yl.shape != (self.N,):
+                raise ValueError("ndxYields must have N entries")
+        Ny = 0 if yl is None else (self.Ns if self.model == MODEL_HYBRID else int(yl.sum()))
+        return j, yl, Ny
+
+    def girf_inputs(self, slot, t0, jump, *, ndxYields=None):
+        """ccmm_chains_girf_inputs: what girf() feeds the simulation for every stored draw of the chains bound to
+        ``slot``, pooled chain slowest (draw c stored + m): dict with Xj (1 + N p + Ny p) x n, SV0 N x n, sqrtPHI
+        N x N x n (lower Cholesky factors of the stored PHI) and info (n; 1 where PHI is not positive definite or
+        not finite, that draw's outputs NaN), the arguments of Context.girf.  t0: 0-based row of the data at the
+        IRF date; jump: the p rows data[t0], data[t0 - 1], ...  The store is kept."""
+        j, yl, Ny = self._girf_args(jump, ndxYields)
+        n = self.stored() * self.B  # room for every chain; the call returns the slot's chain count
+        ldX = 1 + self.N * self.p + Ny * self.p
+        Xj, SV0 = np.zeros((ldX, n), order="F"), np.zeros((self.N, n), order="F")
+        sq, info = np.zeros((self.N, self.N, n), order="F"), np.zeros(n, dtype=np.int32)
+        nC = _check(self.lib.ccmm_chains_girf_inputs(self.handle, int(slot), int(t0), _ptr(j), _ptr(yl, _u8p),
+                                                     _ptr(Xj), _ptr(SV0), _ptr(sq), _ptr(info, _ip)),
+                    "ccmm_chains_girf_inputs")
+        n = self.stored() * nC
+        return dict(Xj=np.asfortranarray(Xj[:, :n]), SV0=np.asfortranarray(SV0[:, :n]),
+                    sqrtPHI=np.asfortranarray(sq[:, :, :n]), info=info[:n])
+
+    def girf(self, slot, t0, jump, H, nsim, shock11, *, pct=None, cumcode=None, np_=12, ndxYields=None,
+             seed=1012023, draws_per_pass=0, keep=False):
+        """ccmm_chains_girf: the generalized impulse responses (generateGIRF2linear.m, generateGIRF2blockhybrid.m,
+        generateGIRF2hybrid.m, by the set's model) of the stored draws of the chains bound to ``slot``, read in
+        place and pooled over its chains (chain slowest), for one date and one or several shock sizes.  t0, jump,
+        ndxYields: as girf_inputs.  pct: the tails' percentiles (default normcdf([-1 1]) 100).  Draw d takes Philox
+        stream d of ``seed``; draws_per_pass: draws simulated at once (0: the most whose workspace stays within
+        1 GB), the results do not depend on it.  Returns a dict (a list of dicts when shock11 is a sequence):
+        fcstYhat, fcstYhat1plus, fcstYhat1minus, IRF1plus, IRF1minus (N x H medians), IRF1plusTails,
+        IRF1minusTails (N x H x nq), quantiles (N x H x nq x 5, the percentiles of all five sets), nbad, for a
+        linear set YhatRB, IRF1RB and their tails (the Rao-Blackwellised responses), and with ``keep``
+        fcstYHATdraws, fcstYHATdraws1plus, fcstYHATdraws1minus (N x H x n; YhatRBdraws, IRF1RBdraws likewise).
+        The store is kept."""
+        j, yl, _ = self._girf_args(jump, ndxYields)
+        scales = np.atleast_1d(np.asarray(shock11, dtype=np.float64)).ravel()
+        ns, N, H = scales.size, self.N, int(H)
+        if pct is None:
+            from math import erf, sqrt
+            pct = [50.0 * (1.0 + erf(x / sqrt(2.0))) for x in (-1.0, 1.0)]
+        pct = _f(np.asarray(pct, float).ravel())
+        nq = pct.size
+        n = self.stored() * self.B  # room for every chain; the call returns the slot's chain count
+        lin = self.model == MODEL_LINEAR
+        cc = None
+        if cumcode is not None:
+            cc = np.asarray(cumcode)
+            if cc.dtype != bool:
+                idx, cc = cc.astype(int).ravel(), np.zeros(N, bool)
+                cc[idx] = True
+            if cc.shape != (N,):
+                raise ValueError("girf: cumcode must have N entries")
+            cc = np.ascontiguousarray(cc, dtype=np.uint8)
+        med = np.zeros((N, H, 5, ns), order="F")
+        qu = np.zeros((N, H, nq, 5, ns), order="F")
+        rmed = np.zeros((N, H, 2, ns), order="F") if lin else None
+        rqu = np.zeros((N, H, nq, 2, ns), order="F") if lin else None
+        dr = np.zeros((N, H, 3, n, ns), order="F") if keep else None
+        rdr = np.zeros((N, H, 2, n, ns), order="F") if keep and lin else None
+        nbad = C.c_int(0)
+        nC = _check(self.lib.ccmm_chains_girf(
+            self.handle, int(slot), int(t0), _ptr(j), H, int(nsim), ns, _ptr(scales), _ptr(cc, _u8p), float(np_),
+            _ptr(yl, _u8p), int(seed), int(draws_per_pass), nq, _ptr(pct) if nq else None, int(bool(keep)),
+            _ptr(med), _ptr(qu) if nq else None, _ptr(rmed), _ptr(rqu) if nq else None, _ptr(dr), _ptr(rdr),
+            C.byref(nbad)), "ccmm_chains_girf")
+        nn = self.stored() * nC
+        if keep and nn != n:  # the buffers were sized for every chain: the call packed [scale][nn draws]
+            dr = np.asfortranarray(dr.ravel(order="F")[:N * H * 3 * nn * ns].reshape((N, H, 3, nn, ns), order="F"))
+            if lin:
+                rdr = np.asfortranarray(rdr.ravel(order="F")[:N * H * 2 * nn * ns].reshape((N, H, 2, nn, ns), order="F"))
+        out = []
+        for s in range(ns):
+            r = {nm: med[:, :, k, s] for k, nm in enumerate(self.GIRF_SETS)}
+            r["IRF1plusTails"], r["IRF1minusTails"] = qu[:, :, :, 3, s], qu[:, :, :, 4, s]
+            r["quantiles"] = qu[..., s]
+            r["nbad"] = int(nbad.value)
+            if lin:
+                for k, nm in enumerate(self.GIRF_RB_SETS):
+                    r[nm], r[nm + "tails"] = rmed[:, :, k, s], rqu[:, :, :, k, s]
+            if keep:
+                for k, nm in enumerate(("fcstYHATdraws", "fcstYHATdraws1plus", "fcstYHATdraws1minus")):
+                    r[nm] = dr[:, :, k, :, s]
+                if lin:
+                    r["YhatRBdraws"], r["IRF1RBdraws"] = rdr[:, :, 0, :, s], rdr[:, :, 1, :, s]
+            out.append(r)
+        return out if np.ndim(shock11) else out[0]
+
+    def poke_stored_phi(self, chain, m, vech):
+        """Test hook (ccmm_chains_poke_stored_phi): overwrite the stored vech(PHI) of stored draw m of ``chain``."""
+        v = np.ascontiguousarray(vech, dtype=np.float64).ravel()
+        if v.size != self.N * (self.N + 1) // 2:
+            raise ValueError("vech must hold N (N + 1) / 2 values")
+        _check(self.lib.ccmm_chains_poke_stored_phi(self.handle, int(chain), int(m), _ptr(v)),
+               "ccmm_chains_poke_stored_phi")
 
     DIAG_SOURCES = {"PAI": 0, "PHI": 1, "invA": 2, "sqrtht": 3, "shadowrate": 4}
 

@@ -4,7 +4,7 @@
 // PS branch, treatment), ccmm_chains_fcst.hip (predictive density, summaries), ccmm_chains_eig.hip (maximum VAR
 // roots, check_stationarity), ccmm_chains_diag.hip (Compute_diagnostics of the stored draws), ccmm_chains_vma.hip
 // (impulse responses of the stored draws and their summaries), ccmm_chains_condmean.hip (conditional mean paths of
-// the stored draws).
+// the stored draws), ccmm_chains_girf.hip (generalized impulse responses of the stored draws).
 #pragma once
 #include "ccmm_host.h"
 #include "ccmm_sweep.h"

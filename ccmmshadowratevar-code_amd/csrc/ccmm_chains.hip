@@ -14,7 +14,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_phi",         "k_store",         "k_gram_chol", "k_elb_prep", "k_elb_cond", "k_elb_gibbs",     "k_elb_rebuild",
     "k_gram_chol_lag", "k_cta_solve_lag", "k_fcst",    "k_gram_big", "k_chol_big", "k_cta_solve_big", "k_astep_big",
     "k_sv_big",      "k_phi_big",       "k_ps_chol",   "k_ps_prop",
-    "k_eig_maxroot", "k_stat_select", "k_diag_series", "k_cond_mean",
+    "k_eig_maxroot", "k_stat_select", "k_diag_series", "k_girf_prep", "k_girf", "k_girf_rb", "k_girf_collect",
+    "k_cond_mean",
     "k_vma",         "k_sum_ffr",     "k_gather_pai", "k_post_stats"};
 
 void ccmm_chains::init(ccmm_ctx* c, const ccmm_chain_config& cf, int nX, int nY) {

@@ -28,6 +28,8 @@ struct GirfArgs {
   double* part;                  // device workspace [M][3][ceil(nsim/4)][H][N]
   double* out;                   // device [M][3][H][N]: baseline, +shock, -shock mean paths
   int force_generic;             // 1: the table-driven kernel even where a specialised one exists
+  int m0;                        // Philox stream id of draw 0 (draw m takes m0 + m); z, svz, part and out are
+                                 // indexed from 0 whatever m0 is
 };
 
 // ---- launch arithmetic (host, no HIP call; tests/launch_plans_main.cpp prints it)

@@ -41,6 +41,7 @@ struct GirfDev {
   const double* z;        // [M][nsim][H][N] or nullptr (Philox)
   const double* svz;      // [M][nsim][H][N] or nullptr
   uint64_t seed;
+  int m0;                 // Philox stream of draw 0
   double* part;           // [M][3][nchunk][H][N]
 };
 
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(128) void k_girf(GirfDev g) {
   Rng rng;
   rng.crn = nullptr;
   rng.seed = g.seed;
-  rng.chain = (uint32_t)mm;
+  rng.chain = (uint32_t)(g.m0 + mm);  // the draw's Philox stream; CRN and output stay relative to the pass
   rng.sweep = 0;
   int head = 0;
   __syncthreads();
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(128) void k_girf_fast(GirfDev g) {
   Rng rng;
   rng.crn = nullptr;
   rng.seed = g.seed;
-  rng.chain = (uint32_t)mm;
+  rng.chain = (uint32_t)(g.m0 + mm);  // the draw's Philox stream; CRN and output stay relative to the pass
   rng.sweep = 0;
   int head = 0;
   __syncthreads();
@@ -405,7 +406,7 @@ hipError_t girf_launch(hipStream_t st, const GirfArgs& a) {
   g.nchunk = (a.nsim + 3) / 4;
   g.PAI = a.PAI; g.invA = a.invA; g.sqrtPHI = a.sqrtPHI; g.SV0 = a.SV0; g.Xj = a.Xj; g.ldX = a.ldX;
   g.actual = a.actual; g.yidx = a.yidx; g.elb = a.elb; g.shock11 = a.shock11; g.z = a.z; g.svz = a.svz;
-  g.seed = a.seed; g.part = a.part;
+  g.seed = a.seed; g.m0 = a.m0; g.part = a.part;
   const GirfPlan pl = girf_plan(a.N, a.p, g.Ny, a.force_generic != 0);
   const dim3 grid(g.nchunk, 3, a.M), block(pl.threads);
   auto go = [&](auto kern) { return launch_k(kern, grid, block, pl.lds, true, st, g); };

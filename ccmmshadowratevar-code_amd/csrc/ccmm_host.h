@@ -106,6 +106,10 @@ enum KernelId {
   KID_EIG,
   KID_STATSEL,
   KID_DIAG,
+  KID_GIRFPREP,
+  KID_GIRF,
+  KID_GIRFRB,
+  KID_GIRFCOLLECT,
   KID_CONDMEAN,
   KID_VMA,
   KID_SUMFFR,

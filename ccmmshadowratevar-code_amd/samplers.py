@@ -36,8 +36,11 @@ def context(device: int = 0) -> _abi.Context:
 def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATSprior,
             ndxYIELDS=None, ELBbound=0.25, check_stationarity=0, yrealized=None, fcstNdraws=None,
             fcstNhorizons=None, rndStream=1012023, doprogress=False, *, nchains=1, device=0,
-            burnin=None, stats=None, Compute_diagnostics=False):
+            burnin=None, stats=None, Compute_diagnostics=False, post=None):
     """mcmcVAR.m (linear BVAR-SV, CTA + A + SV + PHI blocks), nargout == 4.
+
+    post (optional): called as post(ch) with the chain set after the last sweep, while the kept draws are still
+    in its store (doMCMC takes the GIRFs there).
 
     Compute_diagnostics=True (the switch of goVAR.m beside check_stationarity): ``stats`` (a dict) receives
     "diagnostics", the block means of Diagnostics.m:3-25 of the stored draws, taken on the device before the
@@ -77,6 +80,8 @@ def mcmcVAR(thisT, MCMCdraws, p, np_, data0, ydates0, minnesotaPriorMean, doRATS
     _stationarity_stats(ch, check_stationarity, stats)
     if Compute_diagnostics and stats is not None:
         stats["diagnostics"] = _chain_diagnostics(ch, 0)
+    if post is not None:
+        post(ch)
     out = ch.get_draws()
     ch.close()
     res = [out["PAI_all"], out["PHI_all"], out["invA_all"], out["sqrtht_all"]]
@@ -307,13 +312,15 @@ _MODELS = {
 
 def _run_single(model, bm, nchains, MCMCdraws, *, ndxYIELDS, ELBbound, yrealized, fcstNdraws, fcstNhorizons,
                 rndStream, doprogress, device, burnin, gibbsburn, Nproposals, elb_ps=True, missing=False,
-                alternate=False, check_stationarity=0, stats=None, want_ps=True, IRF1scale=None, IRFcumcode=None):
+                alternate=False, check_stationarity=0, stats=None, want_ps=True, IRF1scale=None, IRFcumcode=None,
+                post=None):
     """One vintage ``bm`` as the one-unit chain set of _bh_chain_set with C = nchains, run for the three
     single-vintage samplers.  Returns a namespace of the raw products, each with the trailing chain axis:
     draws (PAI_all, PHI_all, invA_all, sqrtht_all, shadowrate_all, missingrate_all; missingrate_all NaN where
     the sweep kept none), fc (Chains.get_fcst with the paths, or None), ps (Chains.get_ps, or None when no
     sweep proposed or ``want_ps`` is false), yields (bool N) and irf (Chains.get_irf1, or None without
-    IRF1scale).  ``stats`` receives stationarityRedraws."""
+    IRF1scale).  ``stats`` receives stationarityRedraws.  ``post``: called as post(ch) after the last sweep, while
+    the kept draws are still in the store."""
     spec, m, B = _MODELS[model], bm.var, int(nchains)
     burn = MCMCdraws if burnin is None else int(burnin)
     dens = bool(fcstNdraws)
@@ -330,6 +337,8 @@ def _run_single(model, bm, nchains, MCMCdraws, *, ndxYIELDS, ELBbound, yrealized
                           check_stationarity=check_stationarity)
     _run_chain_set(ch, burn, MCMCdraws, doprogress)
     _stationarity_stats(ch, check_stationarity, stats)
+    if post is not None:
+        post(ch)
     ps = ch.get_ps() if use_ps and want_ps else None
     irf = ch.get_irf1() if IRF1scale is not None else None  # (before get_fcst, which resets the records)
     fc = ch.get_fcst(paths=True) if dens else None
@@ -379,7 +388,7 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
                                  yrealized=None, fcstNdraws=None, fcstNhorizons=None,
                                  rndStream=1012023, doprogress=False, *, nchains=1, device=0,
                                  burnin=None, gibbsburn=100, Nproposals=_MODELS["blockhybrid"].Nproposals, elb_ps=True,
-                                 stats=None):
+                                 stats=None, post=None):
     """mcmcVARshadowrateBlockHybrid.m:1-14, outputs PAI_all, PHI_all, invA_all,
     sqrtht_all, shadowrate_all (M x Nshadowrates x elbT), missingrate_all (NaN unless
     doELBsampleAlternate: then the sweep's extra unconstrained draw, :470-478).
@@ -417,7 +426,7 @@ def mcmcVARshadowrateBlockHybrid(thisT, MCMCdraws, p, np_, data0, ydates0, actua
                     gibbsburn=gibbsburn, Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling,
                     alternate=bool(doELBsampling and doELBsampleAlternate),
                     check_stationarity=check_stationarity, stats=stats, want_ps=stats is not None,
-                    IRF1scale=IRF1scale, IRFcumcode=IRFcumcode)
+                    IRF1scale=IRF1scale, IRFcumcode=IRFcumcode, post=post)
     if r.ps is not None:
         stats.update(countELBaccept=r.ps["countAccept"], countELBacceptBurnin=r.ps["countAcceptBurnin"],
                      stackAccept=r.ps["stackAccept"])
@@ -500,7 +509,7 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
                        doELBsampleAlternate, ELBbound, elbT0, check_stationarity=0, IRF1scale=None,
                        IRFcumcode=None, yrealized=None, fcstNdraws=None, fcstNhorizons=None,
                        rndStream=1012023, doprogress=False, *, nchains=1, device=0, burnin=None,
-                       gibbsburn=100, Nproposals=_MODELS["hybrid"].Nproposals, elb_ps=True, stats=None):
+                       gibbsburn=100, Nproposals=_MODELS["hybrid"].Nproposals, elb_ps=True, stats=None, post=None):
     """mcmcVARhybridGibbs.m:1-14, outputs PAI_all (M x K x N, K = 1 + N p + Ns p),
     PHI_all, invA_all, sqrtht_all, shadowrate_all (M x Nshadowrates x elbT),
     missingrate_all (proposal 1 of each sweep's PS draws, :486; NaN with elb_ps=False); with
@@ -532,7 +541,7 @@ def mcmcVARhybridGibbs(thisT, MCMCdraws, p, np_, data0, ydates0, actualrateWeigh
                     yrealized=yrealized, fcstNdraws=fcstNdraws, fcstNhorizons=fcstNhorizons, rndStream=rndStream,
                     doprogress=doprogress, device=device, burnin=burnin, gibbsburn=gibbsburn,
                     Nproposals=Nproposals, elb_ps=elb_ps, missing=not doELBsampling, want_ps=stats is not None,
-                    IRF1scale=IRF1scale, IRFcumcode=IRFcumcode)
+                    IRF1scale=IRF1scale, IRFcumcode=IRFcumcode, post=post)
     if r.ps is not None:
         stats.update(countELBaccept=r.ps["countAccept"] + r.ps["countAcceptBurnin"],
                      stackAccept=r.ps["stackAccept"])
@@ -1954,5 +1963,203 @@ def save_do_mat(filename, res, *, data, ydates, ncode, tcode, cumcode, p=12, MCM
             m[k] = v[:, None] if v.ndim == 1 else v
         else:
             m[k] = float(v)
+    savemat(filename, m, do_compression=True)
+    return filename, sorted(m)
+
+
+# ---------------------------------------------------------------------------
+# The full-sample study: doMCMClinear.m, doMCMCshadowrateBlockHybrid.m, doMCMChybrid.m, doMCMCshadowrate.m and the
+# analogously named generateGIRF2*.m, the GIRFs taken from the draw stores on the device (Chains.girf)
+
+MCMC_FILES = {"linear": "mcmcLinear", "blockhybrid": "mcmcBlockHybrid", "hybrid": "mcmcHybrid",
+              "shadowrate": "mcmcShadowrate"}                                     # the scripts' save lines
+IRF_FILES = {"linear": "irf2Linear", "blockhybrid": "irf2BlockHybrid", "hybrid": "irf2Hybrid"}
+MCMC_NAMES = ("PAI_all", "PHI_all", "invA_all", "sqrtht_all", "shadowrate_all")
+GIRF_SHOCKSIZES = {"fredMD20VXO-2022-09": 1.27, "fredMD20VXOexYield-2022-09": 1.27,      # generateGIRF2blockhybrid.m
+                   "fredblockMD20EBP-2022-09": 0.11, "fredMD20EBP-2022-09": 0.11,        # :126-134
+                   "fredMD20EBPexYield-2022-09": 0.11, "fredMD3EBP-2022-09": 0.11}
+ELB_TAGS = {0.25: "", 0.125: "-ELB125", 0.5: "-ELB500"}                           # doMCMChybrid.m:38-47
+
+
+def girf_shocksize(datalabel):
+    """shocksize of generateGIRF2blockhybrid.m:126-134 (1 for a datalabel the scripts do not list)."""
+    return GIRF_SHOCKSIZES.get(datalabel, 1.0)
+
+
+def datestr_yyyymmm(dn):
+    """datestr(dn, 'yyyymmm') of a MATLAB datenum."""
+    import datetime
+    return datetime.date.fromordinal(int(dn) - 366).strftime("%Y%b")
+
+
+def girf_jump(data, t0, p):
+    """The p jump-off months of Chains.girf: data[t0], data[t0 - 1], .. (t0 the 0-based row of the IRF date)."""
+    t0, p = int(t0), int(p)
+    if t0 - p + 1 < 0:
+        raise ValueError(f"row {t0} leaves no {p} months of data up to it")
+    return np.ascontiguousarray(np.asarray(data, float)[t0 - np.arange(p)])
+
+
+def _pool_chains(a, B):
+    """A sampler's output with its trailing chain axis (B > 1) -> the draws of all chains, chain slowest."""
+    return a if B == 1 else np.moveaxis(a, -1, 0).reshape((-1,) + a.shape[1:-1])
+
+
+def doMCMC(model, data, ydates, ncode, *, jumpDate, p=12, np_=12, MCMCdraws=1000, ELBbound=0.25, doRATSprior=True,
+           check_stationarity=0, seed=1012023, nchains=1, burnin=None, irfDATES=(), irfSCALES=(1,), irfNdraws=1000,
+           irfHorizon=120, shocksize=None, datalabel="fredblockMD20EBP-2022-09", cumcode=None, keep_draws=True,
+           keep_irf_draws=False, draws_per_pass=0, device=0):
+    """The full-sample estimate of one model and its impulse responses: doMCMClinear.m (model="linear"),
+    doMCMCshadowrateBlockHybrid.m ("blockhybrid", doELBsampleAlternate = false as the script passes it),
+    doMCMChybrid.m ("hybrid"), doMCMCshadowrate.m ("shadowrate"), then generateGIRF2linear.m /
+    generateGIRF2blockhybrid.m / generateGIRF2hybrid.m for every irfDATES x irfSCALES.  The sample ends at
+    ``jumpDate`` (a datenum of ``ydates``); the sampler is the single-vintage one of the model (mcmcVAR,
+    mcmcVARshadowrateBlockHybrid, mcmcVARhybridGibbs, mcmcVARshadowrate: same set-up, seed and Philox streams, so the
+    same draws), and the GIRFs are taken by Chains.girf from its draw store in place before the draws are downloaded:
+    pooled over the chains (chain slowest), draw d on Philox stream d of ``seed``, shock11 = IRF1scale shocksize
+    (shocksize None: girf_shocksize(datalabel)), ``cumcode`` (bool N or 0-based indices) the rows cumulated / np_.
+    "shadowrate" has no generateGIRF2 script: a non-empty irfDATES is a ValueError for it.
+
+    Returns dict(mcmc=..., irf=...) and the run's facts (model, thisT, T, elbT0, ndxSHADOWRATE, ndxOTHERYIELDS,
+    shocksize, titlename): mcmc holds PAI_all, PHI_all, invA_all, sqrtht_all (and shadowrate_all) with MCMCdraws
+    nchains draws, chain slowest (empty without ``keep_draws``); irf[(IRF1scale, irfDate)] holds fcstYhat,
+    fcstYhat1plus, fcstYhat1minus, IRF1plus, IRF1plusTails, IRF1minus, IRF1minusTails (N x H; tails N x H x 2 at
+    normcdf([-1 1]) 100), for "linear" YhatRB, YhatRBtails, IRF1RB, IRF1RBtails, and with ``keep_irf_draws``
+    fcstYHATdraws, fcstYHATdraws1plus, fcstYHATdraws1minus (N x H x draws)."""
+    if model not in MCMC_FILES:
+        raise ValueError(f"model must be one of {sorted(MCMC_FILES)}, not {model!r}")
+    irfDATES = [float(d) for d in np.atleast_1d(np.asarray(irfDATES, float)).ravel()]
+    irfSCALES = [float(s) for s in np.atleast_1d(np.asarray(irfSCALES, float)).ravel()]
+    if model == "shadowrate" and irfDATES:
+        raise ValueError("there is no generateGIRF2 script for the shadowrate model: irfDATES must be empty")
+    if ELBbound not in ELB_TAGS:
+        raise ValueError(f"ELBbound value of {ELBbound:5.2f} not recognized")
+    data = np.asarray(data, float)
+    ydates = np.asarray(ydates, float)
+    N, B, M, p = data.shape[1], int(nchains), int(MCMCdraws), int(p)
+    hit = np.flatnonzero(ydates == jumpDate)
+    if hit.size != 1:
+        raise ValueError("jumpDate is not one of ydates")
+    thisT = int(hit[0]) + 1                                                       # 1-based, as the scripts
+    if B < 1 or M < 1 or int(irfNdraws) < 1 or int(irfHorizon) < 1:
+        raise ValueError("nchains, MCMCdraws, irfNdraws and irfHorizon must be >= 1")
+    if irfDATES and not irfSCALES:
+        raise ValueError("irfSCALES is empty")
+    t0s = []
+    for d in irfDATES:
+        h = np.flatnonzero(ydates == d)
+        if h.size != 1 or h[0] >= thisT or h[0] - p < 0:
+            raise ValueError(f"irfDate {d} is not a month of the sample with p months before it")
+        t0s.append(int(h[0]))
+    cum = np.zeros(N, bool)
+    if cumcode is not None:
+        cc = np.asarray(cumcode)
+        if cc.dtype == bool:
+            if cc.shape != (N,):
+                raise ValueError("cumcode must have N entries")
+            cum = cc.copy()
+        else:
+            cum[cc.astype(int).ravel()] = True
+    ndxS, ndxO, ndxY = setShadowYields(ncode, ELBbound)
+    elb = model != "linear"
+    if elb and ndxS.size == 0:
+        raise ValueError("no shadow-rate variable among ncode")
+    elbT0 = elbT0_of(data, ndxS, ELBbound, p) if elb else None
+    shocksize = girf_shocksize(datalabel) if shocksize is None else float(shocksize)
+    mpm = setMinnesotaMean(ncode)
+    yields = _mask(N, ndxY) if elb else None
+    irf = {}
+
+    def post(ch):       # the GIRFs of every date and scale, from the store
+        for d, t0 in zip(irfDATES, t0s):
+            rs = ch.girf(0, t0, girf_jump(data[:, :N], t0, p), int(irfHorizon), int(irfNdraws),
+                         [s * shocksize for s in irfSCALES], cumcode=cum, np_=np_, ndxYields=yields, seed=seed,
+                         draws_per_pass=draws_per_pass, keep=keep_irf_draws)
+            for s, r in zip(irfSCALES, rs):
+                if r.pop("nbad"):
+                    warnings.warn(f"irfDate {d}: draws whose PHI is not positive definite (their paths are NaN)")
+                r.pop("quantiles")
+                irf[(s, d)] = r
+
+    kw = dict(rndStream=seed, nchains=B, device=device, burnin=burnin, post=post if irfDATES else None)
+    if model == "linear":
+        out = mcmcVAR(thisT, M, p, np_, data, ydates, mpm, doRATSprior, ndxYIELDS=ndxY, ELBbound=ELBbound,
+                      check_stationarity=check_stationarity, **kw)
+    elif model == "blockhybrid":
+        out = mcmcVARshadowrateBlockHybrid(thisT, M, p, np_, data, ydates, ~_mask(N, ndxY), mpm, doRATSprior, ndxS,
+                                           ndxO, True, False, ELBbound, elbT0, check_stationarity, **kw)
+    elif model == "hybrid":
+        out = mcmcVARhybridGibbs(thisT, M, p, np_, data, ydates, None, mpm, doRATSprior, ndxS, ndxO, True, False,
+                                 ELBbound, elbT0, check_stationarity, **kw)
+    else:
+        kw.pop("post")
+        out = mcmcVARshadowrate(thisT, M, p, np_, data, ydates, mpm, doRATSprior, False, ndxS, ndxO, True, ELBbound,
+                                elbT0, check_stationarity, **kw)
+    mcmc = {}
+    if keep_draws:
+        names = MCMC_NAMES if elb else MCMC_NAMES[:4]
+        mcmc = {nm: _pool_chains(np.asarray(a), B) for nm, a in zip(names, out)}
+    tag = ELB_TAGS[ELBbound] if elb else ""                                       # doMCMClinear.m:117 has no ELBtag
+    return dict(model=model, mcmc=mcmc, irf=irf, thisT=thisT, T=thisT - p, elbT0=elbT0, ndxSHADOWRATE=ndxS,
+                ndxOTHERYIELDS=ndxO, shocksize=shocksize, MCMCdraws=M, nchains=B, p=p, ELBbound=ELBbound,
+                jumpDate=float(jumpDate), datalabel=datalabel, irfNdraws=int(irfNdraws), irfHorizon=int(irfHorizon),
+                titlename=f"{datalabel}{tag}-p{p}-jumpoff{datestr_yyyymmm(jumpDate)}")
+
+
+def _study_workspace(res, data, ydates, ncode, tcode, cumcode):
+    """The workspace variables both result files of the full-sample study share (1-based indices)."""
+    data = np.asarray(data, float)
+    ndxS1 = np.asarray(res["ndxSHADOWRATE"], int) + 1
+    ndxO1 = np.asarray(res["ndxOTHERYIELDS"], int) + 1
+    m = dict(data=data, ydates=np.asarray(ydates, float)[:, None], p=float(res["p"]), np=12.0,
+             N=float(data.shape[1]), K=float(data.shape[1] * res["p"] + 1),
+             ncode=np.array(list(ncode), dtype=object)[None, :], tcode=np.asarray(tcode, float)[None, :],
+             cumcode=np.asarray(cumcode, bool)[None, :], MCMCdraws=float(res["MCMCdraws"] * res["nchains"]),
+             ELBbound=float(res["ELBbound"]), ndxSHADOWRATE=ndxS1.astype(float)[None, :],
+             ndxOTHERYIELDS=ndxO1.astype(float)[None, :], ndxYIELDS=np.union1d(ndxS1, ndxO1).astype(float)[None, :],
+             datalabel=res["datalabel"], jumpDate=float(res["jumpDate"]), thisT=float(res["thisT"]),
+             T=float(res["T"]), Tdata=float(len(ydates)))
+    if res["elbT0"] is not None:
+        m["elbT0"] = float(res["elbT0"])
+    return m
+
+
+def save_mcmc_mat(filename, res, *, data, ydates, ncode, tcode, cumcode):
+    """The result file of a doMCMC*.m script (save('mcmc<Model>-<titlename>.mat')) from a doMCMC result run with
+    keep_draws, as a v5 MAT-file (scipy.io.savemat) under the workspace's names: the draws PAI_all, PHI_all,
+    invA_all, sqrtht_all (shadowrate_all), the data and the settings.  ``filename`` None: the script's name in the
+    working directory.  Index variables are 1-based as in MATLAB.  Returns (the file's name, the sorted names)."""
+    from scipy.io import savemat
+    if not res["mcmc"]:
+        raise ValueError("the doMCMC result holds no draws (keep_draws=False)")
+    if filename is None:
+        filename = f"{MCMC_FILES[res['model']]}-{res['titlename']}.mat"
+    m = _study_workspace(res, data, ydates, ncode, tcode, cumcode)
+    m.update(titlename=res["titlename"], **res["mcmc"])
+    savemat(filename, m, do_compression=True)
+    return filename, sorted(m)
+
+
+def save_irf_mat(filename, res, IRF1scale, irfDate, *, data, ydates, ncode, tcode, cumcode):
+    """The result file of a generateGIRF2*.m script for one scale and date (save('irf2<Model>-<titlename>.mat'),
+    titlename <datalabel>[ELBtag]-p<p>-IRF1scale<scale>-jumpoff<yyyymmm>-irfDate<yyyymmm>) from a doMCMC result, as
+    a v5 MAT-file under the workspace's names.  ``filename`` None: the script's name in the working directory.
+    Returns (the file's name, the sorted names)."""
+    from scipy.io import savemat
+    model = res["model"]
+    if model not in IRF_FILES:
+        raise ValueError(f"no generateGIRF2 script for model {model!r}")
+    r = res["irf"][(float(IRF1scale), float(irfDate))]
+    tag = ELB_TAGS[res["ELBbound"]] if model != "linear" else ""
+    title = (f"{res['datalabel']}{tag}-p{res['p']}-IRF1scale{int(IRF1scale) if float(IRF1scale).is_integer() else IRF1scale}"
+             f"-jumpoff{datestr_yyyymmm(res['jumpDate'])}-irfDate{datestr_yyyymmm(irfDate)}")
+    if filename is None:
+        filename = f"{IRF_FILES[model]}-{title}.mat"
+    m = _study_workspace(res, data, ydates, ncode, tcode, cumcode)
+    m.update(titlename=title, IRF1scale=float(IRF1scale), irfDate=float(irfDate), shocksize=float(res["shocksize"]),
+             shock11=float(IRF1scale) * float(res["shocksize"]), irfNdraws=float(res["irfNdraws"]),
+             irfHorizon=float(res["irfHorizon"]), prc70=np.array([[_normcdf(-1), _normcdf(1)]]) * 100,
+             ndxIRFT0=float(np.flatnonzero(np.asarray(ydates, float) == irfDate)[0] + 1))
+    m.update({k: np.asarray(v) for k, v in r.items()})
     savemat(filename, m, do_compression=True)
     return filename, sorted(m)

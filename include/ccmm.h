@@ -763,6 +763,45 @@ int ccmm_girf_hybrid(ccmm_ctx* ctx, int M, int N, int p, int H, int nsim, const 
                      const uint8_t* ndxYields, double elb, const uint8_t* cumcode, double np_, double shock11,
                      const double* z, const double* svz, uint64_t seed, double* yhat);
 
+/* The GIRFs of the stored draws of the chains bound to data slot `slot` (contiguous chain indices), read in place
+ * and pooled over the slot's C chains, chain slowest: draw d = c stored + m, n = C stored draws (the full-sample
+ * study: generateGIRF2linear.m / generateGIRF2blockhybrid.m / generateGIRF2hybrid.m over the draws of doMCMC*.m,
+ * by the set's model; the shadowrate model has no such script and is refused).  One date, nscales shock sizes.
+ *   t0: 0-based row of the data at irfDate (ndxIRFT0 - 1); jump: p x N doubles, jump[l N + j] = data(t0 - l, j),
+ *   the months t0, t0 - 1, ..; SV0 is row t0 - p of the draw's sqrtht, sqrtPHI the lower Cholesky factor of its
+ *   PHI, Xjumpoff [1, the p months, the ring of the yields (block hybrid) or of the shadow-rate variables (hybrid)],
+ *   where with n' = t0 + 1 - elbT0 - p > 0 the shadow-rate variables of month t0 - l are month n' - 1 - l of the
+ *   draw's shadow rates when that is >= 0 (generateGIRF2blockhybrid.m:204-218).
+ *   ndxYields: N bytes (the shadow-rate models; NULL for the linear model): the ring and the actual-rate block of
+ *   the block hybrid (actual = not a yield), the output floor of both.  cumcode: N bytes or NULL.
+ *   Draw d is simulated by ccmm_girf's kernels with Philox stream d of `seed`, in passes whose workspace stays
+ *   within 1 GB (draws_per_pass > 0: that many draws per pass); the results do not depend on the pass size.
+ * Outputs (any may be NULL), series i + N h, per scale s:
+ *   median    [nscales][5][H N]: fcstYhat, fcstYhat1plus, fcstYhat1minus, IRF1plus, IRF1minus (medians over the
+ *             draws of base, plus, minus, plus - base, minus - base);  quantiles [nscales][5][nq][H N] (MATLAB
+ *             prctile at pct);
+ *   rbMedian  [nscales][2][H N], rbQuantiles [nscales][2][nq][H N] (linear model): YhatRB and IRF1RB
+ *             (generateGIRF2linear.m:175-216), every equation one fp64 fma chain over the state ascending;
+ *   draws     [nscales][n][3][H][N] (keep != 0): fcstYHATdraws, fcstYHATdraws1plus, fcstYHATdraws1minus;
+ *   rbDraws   [nscales][n][2][H][N] (keep != 0, linear model): YhatRBdraws, IRF1RBdraws;
+ *   nbad      the draws whose PHI is not positive definite or not finite (their paths are NaN).
+ * N <= 32 and K + Ny p + N <= 384.  Returns C (> 0), or a negative error code.  The draw store is left as it is. */
+int ccmm_chains_girf(ccmm_chains* ch, int slot, int t0, const double* jump, int H, int nsim, int nscales,
+                     const double* shock11, const uint8_t* cumcode, double np_, const uint8_t* ndxYields,
+                     uint64_t seed, int draws_per_pass, int nq, const double* pct, int keep, double* median,
+                     double* quantiles, double* rbMedian, double* rbQuantiles, double* draws, double* rbDraws,
+                     int* nbad);
+/* What ccmm_chains_girf feeds the simulation, for every pooled draw: Xj [n][ldX] (ldX = 1 + N p + Ny p), SV0
+ * [n][N], sqrtPHI [n][N][N] (column-major per draw, zeros above the diagonal), info [n] (1: PHI not positive
+ * definite or not finite, the draw's three outputs NaN); any may be NULL.  Returns C. */
+int ccmm_chains_girf_inputs(ccmm_chains* ch, int slot, int t0, const double* jump, const uint8_t* ndxYields,
+                            double* Xj, double* SV0, double* sqrtPHI, int* info);
+
+/* Test hook (tests/test_gpu_girf_store.py): overwrites the stored vech(PHI), N (N + 1) / 2 doubles, of stored draw
+ * m of chain `chain`, so that a draw whose PHI is not positive definite -- which the sampler never produces --
+ * reaches ccmm_chains_girf's screen. */
+int ccmm_chains_poke_stored_phi(ccmm_chains* ch, int chain, int m, const double* vech);
+
 /* ------------------------------------------------------------ diagnostics */
 
 /* psrf(X) of DiagnosticsShadowrate.m:34-128 (== Diagnostics.m:28; Brooks & Gelman 1998, square-root
